@@ -23,6 +23,12 @@ per-rank digest exchange of the first-launch check and the result
 collection (an all-gather of per-universe 64-bit hashes over RCCL/xGMI),
 timed and reported separately.
 
+A plain run (`--gpus N --steps K --warmup W`) fills the input, warms up, times
+the K steps and prints the line; `--dump-outputs DIR` adds the .npy files of
+what the last timed step computed.  Everything else -- the first-launch check,
+the HBM-only and copy figures, the result collection, the side configs, the
+CPU baselines, the detail file -- is a `--full` run's.
+
 Prints ONE JSON line on rank 0 (contract: task brief).
 """
 from __future__ import annotations
@@ -82,12 +88,21 @@ def parse_args(argv=None):
                    help="override: per-rank universes (config 2) or the global total (config 4)")
     p.add_argument("--gens-per-step", type=int, default=1)
     p.add_argument("--seed", type=int, default=-1, help="override the config's seed")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last one computed as DIR/<name>.npy (dump_outputs)")
+    p.add_argument("--full", action="store_true",
+                   help="besides the timed steps: verify the first launch, the HBM-only and copy figures, the "
+                        "result collection, the side configs, the CPU baselines and the detail file "
+                        "(the --no-* options below switch parts of that off)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-seconds", type=float, default=12.0,
                    help="wall budget of the config-2 CPU baseline (half at 1 thread, half on all host cores)")
     p.add_argument("--no-secondary", action="store_true", help="skip the config-3/4/5 side measurements")
     p.add_argument("--no-verify", action="store_true")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 # ----------------------------------------------------------------------------
@@ -613,6 +628,49 @@ def verify_first_launch(hip, rt, out, first, cfg, seed, gens, world, n_rank, n_t
 
 
 # ----------------------------------------------------------------------------
+# --dump-outputs: what the last timed step computed, as .npy files
+# ----------------------------------------------------------------------------
+DUMP_BUDGET_BYTES = 64 * 10 ** 6   # all ranks' files together
+DUMP_BYTES_PER_UNIVERSE = 64 * 4 * 4 + 8   # 64 columns x 4 float32 fields, and the float64 index
+DUMP_SAMPLE_SEED = 64
+
+
+def dump_sample(n: int, world: int) -> np.ndarray:
+    """Which universes of an n-universe shard --dump-outputs writes (sorted
+    local indices): all of them while they fit this rank's share of
+    DUMP_BUDGET_BYTES, else a fixed seeded sample that always holds the
+    shard's first and last universe."""
+    k = (DUMP_BUDGET_BYTES // world - 4096) // DUMP_BYTES_PER_UNIVERSE
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    pick = np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=k - 2, replace=False)
+    return np.union1d(pick, [0, n - 1]).astype(np.int64)
+
+
+def dump_outputs(dirname: str, final: torch.Tensor, first: int, rank: int, world: int) -> dict:
+    """Write the rank's output of the last timed step (`final`, the buffer
+    that step wrote: n universes x 64 columns of 64 bits) as
+      state_words16.npy   float32 [k, 64, 4]: each 64-bit column as its four
+                          16-bit fields, low first (exact in float32);
+      state_universe.npy  float64 [k]: the global index of each universe,
+    for the k universes of dump_sample().  With more than one rank each rank
+    writes its own pair, `_rank<r>` before `.npy`."""
+    idx = dump_sample(final.shape[0], world)
+    words = final[torch.from_numpy(idx).to(final.device)].cpu().numpy().view(np.uint64)
+    fields = (words[:, :, None] >> np.arange(0, 64, 16, dtype=np.uint64)) & np.uint64(0xFFFF)
+    suffix = "" if world == 1 else f"_rank{rank}"
+    os.makedirs(dirname, exist_ok=True)
+    files = {f"state_words16{suffix}.npy": fields.astype(np.float32),
+             f"state_universe{suffix}.npy": (idx + first).astype(np.float64)}
+    for name, arr in files.items():
+        np.save(os.path.join(dirname, name), arr)
+    return {"dir": dirname, "files": sorted(files), "universes_written": int(idx.size),
+            "universes_per_rank": int(final.shape[0]),
+            "sample": "every universe" if idx.size == final.shape[0] else
+                      f"fixed sample (numpy default_rng({DUMP_SAMPLE_SEED}), first and last universe included)"}
+
+
+# ----------------------------------------------------------------------------
 # side measurements at N=1
 # ----------------------------------------------------------------------------
 def secondary_config3(hip, rt, cpu_seconds=0.0):
@@ -1076,14 +1134,14 @@ def main(argv=None):
 
     a = hip.fill_random(n, seed=seed, first_universe=first, device=rt.device, stream=rt.stream)
     b = torch.empty_like(a)
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline
+    want_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
     x_cpu = a[: 1 << 20].cpu().numpy().view(np.uint64).copy() if want_cpu else None
     bufs = [a, b]
 
-    # warmup (untimed); the first launch's output is checked shard by shard
+    # warmup (untimed); a full run checks the first launch's output shard by shard
     hip.step(bufs[0], out=bufs[1], generations=gens, stream=rt.stream)
     verified = None
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         verified = verify_first_launch(hip, rt, bufs[1], first, cfg, seed, gens, world, n_rank, n_total,
                                        shards)
     _, cur = timed_launches(hip, rt, [bufs[1], bufs[0]], max(args.warmup - 1, 0), gens)
@@ -1112,24 +1170,26 @@ def main(argv=None):
     else:
         per_rank = [(span_ms / args.steps, n)]
     final = bufs[cur]
+    dumped = dump_outputs(args.dump_outputs, final, first, rank, world) if args.dump_outputs else None
 
+    # from here to the printed line everything measured or checked is a full run's
     # result collection (not in the timed region): all-gather per-universe hashes
-    h = hip.hashes(final, stream=rt.stream)
+    h = hip.hashes(final, stream=rt.stream) if args.full else None
     rt.sync()
     # side figures on the rank's own buffers (after the hashes: they overwrite
     # both): cache-neutral step and live copy ceilings, gathered per rank
-    figs = stream_figures(hip, rt, final, bufs[1 - cur], gens) if gens <= 2 else None
+    figs = stream_figures(hip, rt, final, bufs[1 - cur], gens) if args.full and gens <= 2 else None
     fig_keys = ("scrubbed_ms", "copy_ms", "copy_neutral_ms", "neutral_ms", "hbm_only_ms")
     fv = [(-1.0 if figs is None or figs[k] is None else figs[k]) for k in fig_keys]
-    if dist_on:
+    if dist_on and args.full:
         ft = torch.tensor(fv, dtype=torch.float64, device=COLL_DEV)
         fparts = [torch.empty_like(ft) for _ in range(world)]
         dist.all_gather(fparts, ft)
         rank_figs = [[(None if x < 0 else float(x)) for x in fp.tolist()] for fp in fparts]
     else:
-        rank_figs = [[(None if x < 0 else x) for x in fv]]
+        rank_figs = [[(None if x < 0 else x) for x in fv]] * world  # a plain run's are all None
     collect = None
-    if dist_on:
+    if dist_on and args.full:
         dist.barrier()
         c0 = time.perf_counter()
         gathered = gather_hashes(h.to(COLL_DEV), world, [c for _, c in shards])
@@ -1142,7 +1202,7 @@ def main(argv=None):
             collect["universes_gathered"] = int(gathered.numel())
 
     secondary = None
-    if rank == 0 and world == 1 and not args.no_secondary and rt.kind == "hip":
+    if args.full and rank == 0 and world == 1 and not args.no_secondary and rt.kind == "hip":
         csec = 0.0 if args.no_cpu_baseline else args.cpu_seconds / 3
         secondary = {"config3": secondary_config3(hip, rt, csec),
                      "config5": secondary_config5(hip, rt),
@@ -1153,7 +1213,7 @@ def main(argv=None):
             torch.cuda.empty_cache()
             secondary["config4"] = secondary_config4_1gpu(hip, rt)
 
-    ceiling, ceiling_src = copy_ceiling(n)
+    ceiling, ceiling_src = copy_ceiling(n) if args.full else (None, None)
     cpu = None
     if want_cpu:
         cpu = cpu_baseline(x_cpu, args.cpu_seconds)
@@ -1168,7 +1228,7 @@ def main(argv=None):
         bpl = n * gens * BYTES_PER_UNIVERSE_GEN
         achieved = bpl / (avg_launch / 1e3) / 1e9 if gens == 1 else None
         agg = sum(c * gens * BYTES_PER_UNIVERSE_GEN / (ms / 1e3) / 1e9 for ms, c in per_rank) if gens == 1 else None
-        traffic, tsrc = load_pmc_traffic(n)
+        traffic, tsrc = load_pmc_traffic(n) if args.full else (None, None)
 
         def gbps(ms, c):
             return c * max(gens, 1) * BYTES_PER_UNIVERSE_GEN / (ms / 1e3) / 1e9 if ms else None
@@ -1250,15 +1310,20 @@ def main(argv=None):
             "cpu_baseline": cpu,
             "verified": verified,
             "collect": collect,
+            "full": args.full,
+            "outputs": dumped,
             "secondary": secondary,
         }
         if rt.kind != "hip":
             line["kernel_backend"] = f"STUB {rt.kind} (CPU rank rehearsal, not a measurement)"
         detail = os.environ.get("LIFEAPI_BENCH_DETAIL", os.path.join(ROOT, "gpurun_out", "bench_detail.json"))
         try:
-            os.makedirs(os.path.dirname(detail), exist_ok=True)
-            with open(detail, "w") as f:
-                json.dump(line, f, indent=1)
+            if args.full:
+                os.makedirs(os.path.dirname(detail), exist_ok=True)
+                with open(detail, "w") as f:
+                    json.dump(line, f, indent=1)
+            else:
+                detail = "not written: a plain run (--full writes it)"
         except OSError as e:
             detail = f"not written: {e}"
         # the side measurements in full stay in the detail file; the flat

@@ -20,11 +20,15 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _bench(*args, timeout=240):
+def _bench(*args, timeout=240, full=True):
+    """One run of bench.py's main() on the stub; a full run (--full: the
+    verification, the side figures and the result collection these tests
+    check) unless `full` is False."""
     env = dict(os.environ, LIFEAPI_BENCH_BACKEND="gloo", HIP_VISIBLE_DEVICES="", CUDA_VISIBLE_DEVICES="",
                MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
+    args = args + ("--full",) if full else args
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "bench_rank_runner.py"), *args], cwd=ROOT, env=env,
                        capture_output=True, text=True, timeout=timeout)
     assert r.returncode == 0, r.stderr[-4000:]
@@ -151,7 +155,7 @@ def test_bench_one_rank_under_launcher_takes_the_collective_path():
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
                         "--master-addr=127.0.0.1", f"--master-port={port}",
                         os.path.join(ROOT, "tests", "bench_rank_runner.py"), "--gpus", "1", "--config", "4",
-                        "--universes", str(1 << 14), "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+                        "--universes", str(1 << 14), "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline",
                         "--no-secondary"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-4000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
@@ -184,3 +188,84 @@ def test_bench_line_is_compact_with_summary_last():
     assert s["c3_kernel_ms"] == 1.3 and s["c3_verified"] is True and s["c3_search_verified"] is True
     assert s["c5_verified"] is True and s["c2_frac_hbm_only"] == 0.7 and s["filter_block_verified"] is True
     assert list(out)[-1] == "secondary_summary" and len(json.dumps(s)) < 1900
+
+
+def _dumped_words(d, suffix=""):
+    """(global universe indices, the u64 columns put together again) of one rank's --dump-outputs files"""
+    f = np.load(os.path.join(d, f"state_words16{suffix}.npy"))
+    u = np.load(os.path.join(d, f"state_universe{suffix}.npy"))
+    assert f.dtype == np.float32 and f.ndim == 3 and f.shape[1:] == (64, 4) and u.dtype == np.float64
+    assert f.shape[0] == u.shape[0] and (f == np.floor(f)).all() and f.min() >= 0 and f.max() < 65536
+    q = f.astype(np.uint64) << np.arange(0, 64, 16, dtype=np.uint64)
+    return u.astype(np.int64), q[..., 0] | q[..., 1] | q[..., 2] | q[..., 3]
+
+
+def test_bench_plain_run_times_the_steps_and_nothing_else():
+    """Without --full the line holds the headline figure of the K timed steps
+    and none of the checks and side measurements (their keys stay, null)."""
+    n = (1 << 11) + 3
+    line, err = _bench("--gpus", "1", "--universes", str(n), "--steps", "3", "--warmup", "2", full=False)
+    assert "torch.distributed.run" not in err
+    assert line["full"] is False and line["steps"] == 3 and line["warmup"] == 2
+    assert line["metric"].startswith("64x64 universe-generations/sec") and line["unit"] == "universe-gen/s"
+    assert line["higher_is_better"] is True and line["dtype"] == "u64"
+    assert line["ms_per_step"] > 0
+    assert line["value"] == pytest.approx(n / (line["ms_per_step"] / 1e3), rel=1e-9)
+    assert line["kernel_ms_avg"] > 0 and line["roofline"]["frac"] > 0
+    for key in ("verified", "collect", "cpu_baseline", "outputs", "value_hbm_only"):
+        assert line[key] is None, key
+    assert line["per_rank"][0]["GBps"] > 0 and line["per_rank"][0]["GBps_hbm_only"] is None
+    assert line["roofline"]["hbm_only"] is None and line["roofline"]["copy_ceiling_recorded_GBps"] is None
+    assert line["detail_file"].startswith("not written")
+    assert set(line["secondary_summary"]) == {"c2_kernel_ms", "c2_frac", "c2_frac_hbm_only", "c2_verified"}
+
+
+def test_bench_dump_outputs_is_the_last_timed_step_and_repeats(tmp_path):
+    """--dump-outputs writes the state the last timed step left (the fill
+    stepped 1 + (W - 1) + K generations), the same files run after run, and
+    K really is the number of timed steps: one more step, one more generation."""
+    from oracle.oracle import Port
+    P = Port()
+    n = (1 << 11) + 3
+    x = P.fill(n, seed=2)
+    runs = {}
+    for name, steps in (("a", 3), ("b", 3), ("c", 4)):
+        d = str(tmp_path / name)
+        line, _ = _bench("--gpus", "1", "--universes", str(n), "--steps", str(steps), "--warmup", "2",
+                         "--dump-outputs", d, full=False)
+        o = line["outputs"]
+        assert o["dir"] == d and o["files"] == ["state_universe.npy", "state_words16.npy"]
+        assert o["universes_written"] == n and o["sample"] == "every universe"
+        assert sorted(os.listdir(d)) == o["files"]
+        u, w = _dumped_words(d)
+        assert (u == np.arange(n)).all()
+        assert (w == P.step_batch(x, 1 + 1 + steps)).all()
+        runs[name] = open(os.path.join(d, "state_words16.npy"), "rb").read()
+    assert runs["a"] == runs["b"] and runs["a"] != runs["c"]
+
+
+def test_bench_dump_outputs_two_ranks(tmp_path):
+    from oracle.oracle import Port
+    P = Port()
+    n = 1 << 12
+    d = str(tmp_path / "out")
+    _bench("--gpus", "2", "--config", "4", "--universes", str(n), "--steps", "2", "--warmup", "1",
+           "--dump-outputs", d, full=False)
+    assert sorted(os.listdir(d)) == ["state_universe_rank0.npy", "state_universe_rank1.npy",
+                                     "state_words16_rank0.npy", "state_words16_rank1.npy"]
+    parts = [_dumped_words(d, f"_rank{r}") for r in range(2)]
+    assert (np.concatenate([u for u, _ in parts]) == np.arange(n)).all()
+    assert (np.concatenate([w for _, w in parts]) == P.step_batch(P.fill(n, seed=4), 1 + 0 + 2)).all()
+
+
+def test_dump_sample_is_fixed_and_within_the_budget():
+    import bench
+    assert bench.DUMP_BUDGET_BYTES == 64 * 10 ** 6
+    assert (bench.dump_sample(1000, 1) == np.arange(1000)).all()
+    for n, world in ((1 << 20, 1), (1 << 24, 1), (1 << 21, 8)):
+        s = bench.dump_sample(n, world)
+        assert s.dtype == np.int64 and (np.diff(s) > 0).all() and s[0] == 0 and s[-1] == n - 1
+        assert (s == bench.dump_sample(n, world)).all()
+        # the two arrays of every rank, with room for the .npy headers
+        assert world * (s.size * (64 * 4 * 4 + 8) + 256) <= bench.DUMP_BUDGET_BYTES
+        assert s.size > 0.9 * bench.DUMP_BUDGET_BYTES / world / (64 * 4 * 4 + 8)

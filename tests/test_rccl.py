@@ -97,7 +97,7 @@ def test_bench_one_rank_rccl_end_to_end():
     env["LIFEAPI_BENCH_DETAIL"] = os.path.join(ROOT, "gpurun_out", "rccl_bench_detail.json")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
                         "--master-addr=127.0.0.1", f"--master-port={_port()}", os.path.join(ROOT, "bench.py"),
-                        "--gpus", "1", "--config", "4", "--steps", "5", "--warmup", "2", "--no-secondary",
+                        "--gpus", "1", "--config", "4", "--steps", "5", "--warmup", "2", "--full", "--no-secondary",
                         "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-4000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])

@@ -10,7 +10,7 @@ O="$R/gpurun_out/prof"
 mkdir -p "$O"
 export TMPDIR=/tmp
 cd /tmp
-B="python3 $R/bench.py --no-cpu-baseline"
+B="python3 $R/bench.py --full --no-cpu-baseline"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$O/trace" -o bench --output-format csv -- $B --steps 50 --warmup 10 > "$O/trace_bench.json" 2> "$O/trace.err" || { tail -20 "$O/trace.err"; exit 2; }
 echo trace ok
 for C in FETCH_SIZE WRITE_SIZE; do
