@@ -23,20 +23,35 @@ using StepFn = void (*)(const uint64_t *, uint64_t *, uint64_t, uint32_t, uint64
 //   generations, as the hand-allocated loop of split_asm.inc; nontemporal
 //   below 32 generations.  One-shot grids: every capped grid-stride grid
 //   measured slower.
-// Batches above kCachedUniverses run with at most 7 blocks (28 waves)
-// resident per CU instead of the 8 its registers allow, set by unused dynamic
-// LDS: fewer concurrent streams per CU, better served by HBM.  Round 3,
-// exact caps (host.hip occupancy_lds), same process, ping-pong with the
-// batch-keyed order (tools/ab/order_interleave_ab.py --caps,
-// profiles/r03/order_caps.jsonl): 8M universes 6.25 TB/s with 7 and 6.22
-// with 6 against 6.09 uncapped and 5.76 with 5; 16M 6.13 with 6 or 7 against
-// 5.95 uncapped and 5.71 with 5; at 4M 7 and uncapped equal (6.44 / 6.39),
-// at 1M-3M uncapped best (7 is 3-4 % slower, 6 up to 7 %).  The fixed-order
-// sweep agrees (tools/ab/step_occupancy_ab.py, profiles/r03/step_occupancy.jsonl:
-// 16M 6.09 / 6.07 TB/s with 6 / 7 against 5.78 uncapped and 5.67 with 5).
-// Round 2 shipped "6", but its LDS arithmetic rounded the share up and gave
-// one block fewer whenever the cap did not divide 160 KiB (6 -> 5, 7 -> 6):
-// it ran 5; occupancy_lds now checks the count on the occupancy API.
+//
+// The streaming step, round 7 (tools/step_store_ab.py, same process, both
+// bodies interleaved round by round, 20 launches per event pair;
+// profiles/r07/step_store_ab/*.jsonl, profiles/r07/README.md).  A wave of
+// k_step now issues its 4 stores back to back and ends behind them
+// (step_kernels.hpp step_group); round 6's body waited for each store before
+// the next.  Under round 6's launch policy the new body is 3.1 % faster at 1M
+// universes (0.1475 against 0.1522 ms, 4.7 x the old body's round-to-round
+// spread, rounds disjoint), 2.5 % at 512K, equal at 4M and 16M, and slower at
+// 2M and 8M (+3.2 %, +0.9 %): a wave that no longer holds its slot through its
+// stores wants fewer waves resident.  The sweep on the new body (universes per
+// wave {4, 8} x resident blocks per CU {all 8, 7, 6} x plain tail x order, or
+// x XCD chunks above 4M) moved these, each by more than 3 x the spread:
+// * resident blocks per CU (unused dynamic LDS, host.hip occupancy_lds): 7
+//   at 1M universes (0.1461 against 0.1475 ms uncapped), 6 from 2M on (2M
+//   0.3131 against 0.3216 uncapped and 0.3167 with 7; 4M 0.6571 against
+//   0.6810 / 0.6722; 8M 1.296 against 1.318 / 1.303; 16M 2.664 against 3.011
+//   / 2.846).  At 512K 7 blocks gained 1.1 %, 1.4 x the spread: not enough,
+//   so batches below 1M stay uncapped; between two measured sizes the cap is
+//   the smaller one's.  Round 6 ran uncapped up to 4M and 7 above.
+// * 4 universes per wave above 4M too (round 4 chose 8 there for 8M): 8M 1.296
+//   against 1.342 ms, 16M 2.664 against 2.702, both at 6 blocks.
+// Unchanged, because nothing beat them: the alternating order with the last
+// min(256 MiB, half the batch) stored plain up to 4M (every other tail or a
+// fixed order 7-15 % slower at 1M), and XCD chunks above (16M: the plain block
+// mapping is 0.7 % faster at 6 blocks, 8M: 2.4 % slower).
+// Against round 6's launch, same process: 512K -2.5 %, 1M -4.0 %, 2M +0.4 %
+// (inside the spread), 4M -3.2 %, 8M -3.2 %, 16M -1.8 %.
+//
 // Launch order and store policy (tools/ab/order_ab.py, profiles/r02/order_*.jsonl,
 // same process, ping-pong as the bench): a launch whose input batch an
 // earlier launch wrote takes the groups in the reverse of that launch's order
@@ -44,15 +59,15 @@ using StepFn = void (*)(const uint64_t *, uint64_t *, uint64_t, uint32_t, uint64
 // written last; the groups that store the last min(256 MiB, half
 // the batch) of a launch use plain stores, which leave that part in the 256 MB
 // memory-side Infinity Cache, and the rest nontemporal ones, which do not
-// evict it.  Batches of up to kCachedUniverses use every block slot, larger
-// ones the cap.  Against round 2's launch (nontemporal, one order, capped at
-// what turned out to be 5 blocks per CU): +12 % at 1M universes, +10 % at 2M,
-// +3-5 % at 512K and 4M, equal at 8M-16M -- most of it from dropping the cap:
-// against one fixed order with every store nontemporal and no cap the order
-// policy gains +1-4 % at 1M (round 3's same-process A/B +4 %, round 4's
-// footprint sweeps +1-2 %, profiles/r04/r04e/footprint.jsonl).
+// evict it.
 constexpr uint64_t kCachedUniverses = 1ull << 22;
-constexpr int kStreamResidentBlocks = 7;
+// resident blocks per CU of the streaming step (0 = as many as fit, 8)
+constexpr uint64_t kCap7Universes = 1ull << 20;  // 7 from here
+constexpr uint64_t kCap6Universes = 1ull << 21;  // 6 from here
+constexpr int kStreamResidentBlocks = 6;
+int stream_resident_blocks(uint64_t n) {
+  return n < kCap7Universes ? 0 : n < kCap6Universes ? 7 : kStreamResidentBlocks;
+}
 // Below this batch size the order stays fixed: at 64K universes (64 MiB per
 // launch) the fixed order was 4 % faster, single batch and two interleaved,
 // and at 128K the two boxes disagreed (-4 / +1 %); from 192K on the
@@ -67,19 +82,11 @@ constexpr const char *kStreamName =
     "each launch stored plain, the rest nt>";
 // Above kCachedUniverses there is no Infinity Cache reuse to arrange: one
 // order, every store nontemporal, and each XCD streams a contiguous eighth
-// of the batch (kXcdChunk, device.hpp xcd_chunk_block).  Same process,
-// ping-pong, 7 blocks per CU (tools/ab/step_xcd_ab.py,
-// profiles/r03/step_xcd_ab.jsonl): 16M universes 2.736 ms against 2.836 for
-// the order/plain-tail launch and 2.845 with the plain block mapping; 8M
-// 1.396 against 1.410 / 1.427; at 4M the chunked mapping was 1 % slower, at
-// 1M equal.
-// Round 4: 8 universes per wave for these batches (4 KiB in flight per
-// wave): same process, interleaved, 7 rounds (tools/ab/big_upw_ab.py,
-// profiles/r04/r04d/big_upw_ab.jsonl): 8M 6.12 against 5.83 TB/s back to
-// back (6.40 / 6.17 after a read-only scrub), 16M and 4M equal (6.38 / 6.38,
-// 6.40 / 6.36).
+// of the batch (kXcdChunk, device.hpp xcd_chunk_block; round 3,
+// profiles/r03/step_xcd_ab.jsonl: 16M 2.736 ms against 2.845 with the plain
+// block mapping at 7 blocks of 8 universes per wave).
 constexpr const char *kStreamBigName =
-    "k_step<dpp, 8 universes/wave, nt, 7-LUT network; each XCD a contiguous eighth, one order>";
+    "k_step<dpp, 4 universes/wave, nt, 7-LUT network; each XCD a contiguous eighth, one order>";
 struct StepLaunch {
   StepFn fn;
   uint64_t universes_per_wave;
@@ -91,10 +98,10 @@ struct StepLaunch {
 };
 StepLaunch shipped_step(uint32_t gens, uint64_t n) {
   if (gens <= 2 && n > kCachedUniverses)
-    return {k_step<XDPP, 8, true, 3, true>, 8, kStreamResidentBlocks, false, 0, kStreamBigName, kXcdChunk};
+    return {k_step<XDPP, 4, true, 3, true, true>, 4, stream_resident_blocks(n), false, 0, kStreamBigName, kXcdChunk};
   if (gens <= 2)
-    return {k_step<XDPP, 4, true, 3, true>, 4, 0, true, std::min<uint64_t>(kPlainBytes, n * 512 / 2), kStreamName,
-            0u};
+    return {k_step<XDPP, 4, true, 3, true, true>, 4, stream_resident_blocks(n), true,
+            std::min<uint64_t>(kPlainBytes, n * 512 / 2), kStreamName, 0u};
   if (gens < 32)
     return {k_step_split<8, 1, true, 6, kAsmLoop>, 4, 0, false, 0,
             "k_step_split<8-way split, 4 universes/wave, nt, 6-LUT tail, assembly loop>", 0u};
@@ -129,7 +136,10 @@ int lifeapi_step_batch_dev(const uint64_t *d_in, uint64_t *d_out, size_t n, uint
   uint32_t order = 0;
   if (l.alternate && n >= kOrderMinUniverses) order = launch_reverse(d_in, d_out, (uint64_t)n * 512) ? kReverse : 0u;
   else note_forward_write(d_out, (uint64_t)n * 512);
-  hipLaunchKernelGGL(l.fn, dim3(grid_for(waves, cus, 0)), dim3(kBlock), lds, (hipStream_t)stream, d_in,
+  // one-shot: k_step's waves take one group each (step_body ONESHOT)
+  const unsigned grid = grid_for(waves, cus, 0);
+  if ((uint64_t)grid * kWavesPerBlock < waves) return fail(LIFEAPI_E_INVALID, "batch too large for one grid%s");
+  hipLaunchKernelGGL(l.fn, dim3(grid), dim3(kBlock), lds, (hipStream_t)stream, d_in,
                      d_out, (uint64_t)n, generations | order | l.flags, plain < waves ? waves - plain : (uint64_t)0);
   return launched("k_step launch");
 }

@@ -129,7 +129,53 @@ constexpr uint32_t kReverse = 1u << 31;
 // groups (xcd_chunk_block); the launcher sets it for large batches.
 constexpr uint32_t kXcdChunk = 1u << 30;
 // NTS: nontemporal stores (default: as the loads) before `plain_from`.
-template <int X, int U, bool NT, int RULE, bool NTS>
+//
+// One group of U universes from u0 on.  FULL: all U lie below n, so loads and
+// stores are unconditional and the wave's memory schedule is U loads back to
+// back, each universe's generations behind a wait for its own load only, and
+// U stores back to back.  gfx9's vmcnt counts stores with loads, and a store
+// under a branch of its own (the ragged form, FULL = false) makes the
+// compiler wait for everything outstanding before every store: the stores of
+// a wave then complete one after another.
+template <int X, int U, bool NT, int RULE, bool NTS, bool FULL>
+__device__ __forceinline__ void step_group(const uint64_t *in, uint64_t *out, uint64_t n, uint32_t gens,
+                                           uint64_t u0, bool nts, uint64_t *slot, int lane) {
+  W a[U];
+#pragma unroll
+  for (int k = 0; k < U; ++k)
+    a[k] = (FULL || u0 + k < n) ? ld<NT>(in + (u0 + k) * kWave + lane) : W{0u, 0u};
+  if constexpr (RULE == 4) {
+#pragma unroll
+    for (int k = 0; k < U; ++k) a[k] = to_eo(a[k]);
+  }
+  for (uint32_t g = 0; g < gens; ++g) {
+#pragma unroll
+    for (int k = 0; k < U; ++k) a[k] = life_gen<X, RULE>(a[k], slot + k * 2 * kWave, lane);
+  }
+  if constexpr (RULE == 4) {
+#pragma unroll
+    for (int k = 0; k < U; ++k) a[k] = from_eo(a[k]);
+  }
+  if (nts) {
+#pragma unroll
+    for (int k = 0; k < U; ++k)
+      if (FULL || u0 + k < n) st<NTS>(out + (u0 + k) * kWave + lane, a[k]);
+  } else {
+    // (the two comments keep the arms apart: unconditional stores to the same
+    // addresses in both are hoisted or sunk into one run, which loses the
+    // nontemporal hint -- metadata to the optimiser)
+    if constexpr (FULL) asm volatile("; plain-stored tail");
+#pragma unroll
+    for (int k = 0; k < U; ++k)
+      if (FULL || u0 + k < n) st<false>(out + (u0 + k) * kWave + lane, a[k]);
+    if constexpr (FULL) asm volatile("; plain-stored tail end");
+  }
+}
+
+// ONESHOT: the grid has a wave for every group (grid_for(groups, cus, 0), as
+// every launch of the product), so a wave takes one group and ends behind its
+// stores without waiting for them; else waves stride over the groups.
+template <int X, int U, bool NT, int RULE, bool NTS, bool ONESHOT = false>
 __device__ __forceinline__ void step_body(const uint64_t *in, uint64_t *out, uint64_t n, uint32_t gens,
                                           uint64_t plain_from) {
   __shared__ uint64_t lds[uses_lds(X) ? kWavesPerBlock * U * 2 * kWave : 1];
@@ -141,49 +187,32 @@ __device__ __forceinline__ void step_body(const uint64_t *in, uint64_t *out, uin
   const uint64_t blk = (gens & kXcdChunk) ? xcd_chunk_block() : (uint64_t)blockIdx.x;
   gens &= ~(kReverse | kXcdChunk);
   const uint64_t groups = (n + U - 1) / U, wstride = (uint64_t)gridDim.x * kWavesPerBlock;
-  for (uint64_t grp = blk * kWavesPerBlock + wib; grp < groups; grp += wstride) {
+  uint64_t *slot = lds + (uses_lds(X) ? wib * U * 2 * kWave : 0);
+  auto group = [&](uint64_t grp) __attribute__((always_inline)) {
     const uint64_t u0 = (rev ? groups - 1 - grp : grp) * U;
-    W a[U];
-#pragma unroll
-    for (int k = 0; k < U; ++k)
-      a[k] = (u0 + k < n) ? ld<NT>(in + (u0 + k) * kWave + lane) : W{0u, 0u};
-    if constexpr (RULE == 4) {
-#pragma unroll
-      for (int k = 0; k < U; ++k) a[k] = to_eo(a[k]);
-    }
-    for (uint32_t g = 0; g < gens; ++g) {
-#pragma unroll
-      for (int k = 0; k < U; ++k)
-        a[k] = life_gen<X, RULE>(a[k], lds + (wib * U + k) * 2 * kWave, lane);
-    }
-    if constexpr (RULE == 4) {
-#pragma unroll
-      for (int k = 0; k < U; ++k) a[k] = from_eo(a[k]);
-    }
-    if (grp < plain_from) {
-#pragma unroll
-      for (int k = 0; k < U; ++k)
-        if (u0 + k < n) st<NTS>(out + (u0 + k) * kWave + lane, a[k]);
-    } else {
-#pragma unroll
-      for (int k = 0; k < U; ++k)
-        if (u0 + k < n) st<false>(out + (u0 + k) * kWave + lane, a[k]);
-    }
+    if (u0 + U <= n) step_group<X, U, NT, RULE, NTS, true>(in, out, n, gens, u0, grp < plain_from, slot, lane);
+    else step_group<X, U, NT, RULE, NTS, false>(in, out, n, gens, u0, grp < plain_from, slot, lane);
+  };
+  const uint64_t first = blk * kWavesPerBlock + wib;
+  if constexpr (ONESHOT) {
+    if (first < groups) group(first);
+  } else {
+    for (uint64_t grp = first; grp < groups; grp += wstride) group(grp);
   }
 }
 
-template <int X, int U, bool NT, int RULE, bool NTS = NT>
+template <int X, int U, bool NT, int RULE, bool NTS = NT, bool ONESHOT = false>
 __global__ __launch_bounds__(kBlock) void k_step(const uint64_t *in, uint64_t *out, uint64_t n,
                                                  uint32_t gens, uint64_t plain_from) {
-  step_body<X, U, NT, RULE, NTS>(in, out, n, gens, plain_from);
+  step_body<X, U, NT, RULE, NTS, ONESHOT>(in, out, n, gens, plain_from);
 }
 // The same kernel under another name, for the tuning build's side launches
 // (bench.py's cache-neutral and copy figures, the order A/Bs), so that a
 // rocprofv3 trace of the bench tells them from the product's launches.
-template <int X, int U, bool NT, int RULE, bool NTS = NT>
+template <int X, int U, bool NT, int RULE, bool NTS = NT, bool ONESHOT = false>
 __global__ __launch_bounds__(kBlock) void k_step_ab(const uint64_t *in, uint64_t *out, uint64_t n,
                                                     uint32_t gens, uint64_t plain_from) {
-  step_body<X, U, NT, RULE, NTS>(in, out, n, gens, plain_from);
+  step_body<X, U, NT, RULE, NTS, ONESHOT>(in, out, n, gens, plain_from);
 }
 
 // step_body with the wave's U universes moved through LDS (the LifeStable
@@ -331,7 +360,10 @@ __global__ __launch_bounds__(WPB * kWave) void k_step_split(const uint64_t *in, 
 // X / RULE: the exchange and network of the generation (life_gen).  PF: each
 // wave loads the next group's states before it works on the current one (a
 // grid of at most the resident waves, looping over the batch).
-template <int U, bool WIDE = false, int X = XDPP, int RULE = 3, bool PF = false>
+// FAST (the 8-byte form on a one-shot grid, a wave for every group): a full
+// group loads and stores unconditionally and the wave ends behind its stores,
+// as step_group's FULL path; the ragged last group keeps the guards.
+template <int U, bool WIDE = false, int X = XDPP, int RULE = 3, bool PF = false, bool FAST = false>
 __global__ __launch_bounds__(kBlock) void k_step_contains(const uint64_t *in, uint64_t *fin,
                                                           const uint64_t *__restrict__ wanted,
                                                           const uint64_t *__restrict__ unwanted,
@@ -352,6 +384,7 @@ __global__ __launch_bounds__(kBlock) void k_step_contains(const uint64_t *in, ui
   uint64_t *st_w = stage + (WIDE || uses_lds(X) ? wib * U * kWave : 0);
   const int half = lane >> 5, col = (lane & 31) * 2;
   static_assert(!(PF && WIDE), "the prefetching loop is the 8-byte form's");
+  static_assert(!(FAST && (PF || WIDE)), "the one-shot fast path is the plain 8-byte form's");
   W an[U];
   auto load_group = [&](uint64_t g, W (&dst)[U]) __attribute__((always_inline)) {
     const uint64_t v0 = (rev ? groups - 1 - g : g) * U;
@@ -362,7 +395,9 @@ __global__ __launch_bounds__(kBlock) void k_step_contains(const uint64_t *in, ui
     const uint64_t g0 = blk * kWavesPerBlock + wib;
     if (g0 < groups) load_group(g0, an);
   }
-  for (uint64_t grp = blk * kWavesPerBlock + wib; grp < groups; grp += wstride) {
+  // one group; full_c: all of its U universes lie below n (FAST only)
+  auto group = [&](uint64_t grp, auto full_c) __attribute__((always_inline)) {
+    constexpr bool FULL = decltype(full_c)::value;
     const uint64_t u0 = (rev ? groups - 1 - grp : grp) * U;
     W a[U];
     if constexpr (PF) {
@@ -387,7 +422,8 @@ __global__ __launch_bounds__(kBlock) void k_step_contains(const uint64_t *in, ui
       __builtin_amdgcn_wave_barrier();  // (the final states reuse the stage below)
     } else {
 #pragma unroll
-      for (int k = 0; k < U; ++k) a[k] = (u0 + k < n) ? ld<true>(in + (u0 + k) * kWave + lane) : W{0u, 0u};
+      for (int k = 0; k < U; ++k)
+        a[k] = (FULL || u0 + k < n) ? ld<true>(in + (u0 + k) * kWave + lane) : W{0u, 0u};
     }
     uint32_t hit[U];
 #pragma unroll
@@ -399,6 +435,15 @@ __global__ __launch_bounds__(kBlock) void k_step_contains(const uint64_t *in, ui
         if (hit[k] == 0 && wave_contains(a[k], w, uw)) hit[k] = g;
       }
     }
+    // lanes 0..U-1 write the U first-hit generations with one store (FULL:
+    // ahead of the final states, whose registers it would else wait for)
+    auto store_first = [&]() __attribute__((always_inline)) {
+      uint32_t h = hit[0];
+#pragma unroll
+      for (int k = 1; k < U; ++k) h = lane == k ? hit[k] : h;
+      if (lane < U && (FULL || u0 + lane < n)) first[u0 + lane] = h;
+    };
+    if constexpr (FULL) store_first();
     if constexpr (WIDE) {
       if (fin) {
 #pragma unroll
@@ -420,17 +465,25 @@ __global__ __launch_bounds__(kBlock) void k_step_contains(const uint64_t *in, ui
     } else if (fin && grp < plain_from) {
 #pragma unroll
       for (int k = 0; k < U; ++k)
-        if (u0 + k < n) st<true>(fin + (u0 + k) * kWave + lane, a[k]);
+        if (FULL || u0 + k < n) st<true>(fin + (u0 + k) * kWave + lane, a[k]);
     } else if (fin) {
+      // (the comments keep this arm apart from the nontemporal one: step_group)
+      if constexpr (FULL) asm volatile("; plain-stored tail");
 #pragma unroll
       for (int k = 0; k < U; ++k)
-        if (u0 + k < n) st<false>(fin + (u0 + k) * kWave + lane, a[k]);
+        if (FULL || u0 + k < n) st<false>(fin + (u0 + k) * kWave + lane, a[k]);
+      if constexpr (FULL) asm volatile("; plain-stored tail end");
     }
-    // lanes 0..U-1 write the U first-hit generations with one store
-    uint32_t h = hit[0];
-#pragma unroll
-    for (int k = 1; k < U; ++k) h = lane == k ? hit[k] : h;
-    if (lane < U && u0 + lane < n) first[u0 + lane] = h;
+    if constexpr (!FULL) store_first();
+  };
+  if constexpr (FAST) {
+    const uint64_t grp = blk * kWavesPerBlock + wib;
+    if (grp < groups) {
+      if ((rev ? groups - 1 - grp : grp) * U + U <= n) group(grp, std::true_type{});
+      else group(grp, std::false_type{});
+    }
+  } else {
+    for (uint64_t grp = blk * kWavesPerBlock + wib; grp < groups; grp += wstride) group(grp, std::false_type{});
   }
 }
 

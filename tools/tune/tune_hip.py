@@ -79,22 +79,25 @@ def step_clock(states: torch.Tensor, out: torch.Tensor, generations: int, stream
     return out, stamps
 
 
-lib.lifeapi_tune_step_order.argtypes = [_vp, _vp, _sz, _u32, _vp, _int, _int, _int, ctypes.c_uint64]
-lib.lifeapi_tune_step_order.restype = _int
+lib.lifeapi_tune_step_order_body.argtypes = [_vp, _vp, _sz, _u32, _vp, _int, _int, _int, ctypes.c_uint64, _int]
+lib.lifeapi_tune_step_order_body.restype = _int
+STEP_BODIES = {"r7": 7, "r6": 6}
 
 
 def step_order(states: torch.Tensor, out: torch.Tensor, generations: int = 1, reverse: bool = False,
                nts: bool = True, resident: int = 6, upw: int = 4, plain_bytes: int = 0,
-               stream=None, xcd_chunk: bool = False) -> torch.Tensor:
+               stream=None, xcd_chunk: bool = False, body: str = "r7") -> torch.Tensor:
     """The shipped gens <= 2 kernel with nontemporal or plain stores, at most
     `resident` blocks per CU, `upw` universes per wave, universes taken in
     reverse order if asked; plain stores for the groups that store the last
-    `plain_bytes` of the launch's order whatever `nts` says."""
+    `plain_bytes` of the launch's order whatever `nts` says.  body: "r7" the
+    product's step_body (k_step_ab), "r6" round 6's (k_step_r6: every store
+    behind a wait for all of the wave's memory operations)."""
     n = hip._universes(states)
-    hip._check(lib.lifeapi_tune_step_order(states.data_ptr(), out.data_ptr(), n,
-                                           generations | ((1 << 31) if reverse else 0) |
-                                           ((1 << 30) if xcd_chunk else 0), hip._stream(stream),
-                                           1 if nts else 0, resident, upw, plain_bytes))
+    hip._check(lib.lifeapi_tune_step_order_body(states.data_ptr(), out.data_ptr(), n,
+                                                generations | ((1 << 31) if reverse else 0) |
+                                                ((1 << 30) if xcd_chunk else 0), hip._stream(stream),
+                                                1 if nts else 0, resident, upw, plain_bytes, STEP_BODIES[body]))
     return out
 
 

@@ -10,6 +10,7 @@
 
 #include "lifeapi_tune.h"
 #include "step_kernels.hpp"
+#include "step_r6.hpp"
 #include "split_asm_tune.inc"
 #include "tile_asm.inc"
 #include "pair_asm.inc"
@@ -579,9 +580,11 @@ int lifeapi_tune_step_contains_nat(const uint64_t *d_in, uint64_t *d_final, cons
         : upw == 132 ? (Fn)k_step_contains<4, false, XDPP, 3, true> : upw == 136 ? (Fn)k_step_contains<8, false, XDPP, 3, true>
         : upw == 200 ? (Fn)k_step_contains<8, false, XDPP, 14, true>
         : upw == 16 ? (Fn)k_step_contains<16> : upw == 12 ? (Fn)k_step_contains<12>
+        // 256 + 8: full groups unconditional, one group per wave (FAST; a one-shot grid, resident >= 0)
+        : upw == 264 && resident >= 0 ? (Fn)k_step_contains<8, false, XDPP, 3, false, true>
         : nullptr;
   if (!fn) return fail(LIFEAPI_E_INVALID, "universes per wave: 1, 2, 4 or 8 (16 + 2, 4, 8: 16-byte form)%s");
-  if (upw > 16 && (((uintptr_t)d_in | (uintptr_t)d_final) & 15u))
+  if (upw > 16 && upw < 256 && (((uintptr_t)d_in | (uintptr_t)d_final) & 15u))
     return fail(LIFEAPI_E_INVALID, "the 16-byte form needs 16-byte aligned batches%s");
   const int universes_per_wave = upw == 16 ? 16 : upw == 12 ? 12 : upw & 15;
   if (resident > 0) {
@@ -683,23 +686,35 @@ int lifeapi_tune_step_pair(const uint64_t *d_in, uint64_t *d_out, size_t n, uint
   return launched("k_step_pair launch");
 }
 
-/* the shipped gens <= 2 kernel (k_step<dpp, U, nt loads, rule 3>) with
- * nontemporal (nts = 1) or plain stores (0), but plain for the groups that
+/* the shipped gens <= 2 kernel (k_step<dpp, U, nt loads, rule 3>, one-shot)
+ * with nontemporal (nts = 1) or plain stores (0), but plain for the groups that
  * store the last `plain_bytes` of the launch's order, at most `resident` blocks per CU
  * (0 = as many as fit), U = upw universes per wave (2, 4 or 8; shipped 4);
- * bit 31 of `generations` reverses the group order                         */
+ * bit 31 of `generations` reverses the group order; body 7 = the product's
+ * step_body, 6 = round 6's (step_r6.hpp; upw 2, 4 or 8 only)               */
 extern "C++" {
 template <int U>
-StepFn order_fn(int nts) { return nts ? k_step_ab<XDPP, U, true, 3, true> : k_step_ab<XDPP, U, true, 3, false>; }
+StepFn order_fn(int nts, int body) {
+  if (body == 6) return nts ? k_step_r6<XDPP, U, true, 3, true> : k_step_r6<XDPP, U, true, 3, false>;
+  return nts ? k_step_ab<XDPP, U, true, 3, true, true> : k_step_ab<XDPP, U, true, 3, false, true>;
+}
 }
 
 int lifeapi_tune_step_order(const uint64_t *d_in, uint64_t *d_out, size_t n, uint32_t generations, void *stream,
                             int nts, int resident, int upw, uint64_t plain_bytes) {
+  return lifeapi_tune_step_order_body(d_in, d_out, n, generations, stream, nts, resident, upw, plain_bytes, 7);
+}
+
+int lifeapi_tune_step_order_body(const uint64_t *d_in, uint64_t *d_out, size_t n, uint32_t generations, void *stream,
+                                 int nts, int resident, int upw, uint64_t plain_bytes, int body) {
   int rc = check_batch(d_in, d_out, n);
   if (rc != LIFEAPI_OK || n == 0) return rc;
   if ((generations & ~(kReverse | kXcdChunk)) > 2) return fail(LIFEAPI_E_INVALID, "streaming step: generations <= 2%s");
   // upw 32 + U: the column-pair form (k_step_pairnat<U>, 16-byte accesses; 16-byte-aligned batches)
-  const StepFn fn = upw == 2 ? order_fn<2>(nts) : upw == 4 ? order_fn<4>(nts) : upw == 8 ? order_fn<8>(nts)
+  if (body != 6 && body != 7) return fail(LIFEAPI_E_INVALID, "step body: 6 or 7%s");
+  if (body == 6 && upw > 8) return fail(LIFEAPI_E_INVALID, "round 6's body: 2, 4 or 8 universes per wave%s");
+  const StepFn fn = upw == 2 ? order_fn<2>(nts, body) : upw == 4 ? order_fn<4>(nts, body)
+                  : upw == 8 ? order_fn<8>(nts, body)
                   : upw == 36 ? (nts ? (StepFn)k_step_pairnat<4, true> : (StepFn)k_step_pairnat<4, false>)
                   : upw == 40 ? (nts ? (StepFn)k_step_pairnat<8, true> : (StepFn)k_step_pairnat<8, false>)
                   // upw 64 + U / 96 + U: through LDS (k_step_dma<U>, 8-byte / 16-byte stores; 16-byte-aligned batches)
@@ -719,7 +734,9 @@ int lifeapi_tune_step_order(const uint64_t *d_in, uint64_t *d_out, size_t n, uin
     if (rc != LIFEAPI_OK) return rc;
   }
   const uint64_t groups = (n + upw - 1) / upw, plain = (plain_bytes + upw * 512 - 1) / (upw * 512);
-  hipLaunchKernelGGL(fn, dim3(grid_for(groups, cus, 0)), dim3(kBlock), lds, (hipStream_t)stream, d_in, d_out,
+  const unsigned grid = grid_for(groups, cus, 0);  // one-shot (k_step_ab's waves take one group each)
+  if ((uint64_t)grid * kWavesPerBlock < groups) return fail(LIFEAPI_E_INVALID, "batch too large for one grid%s");
+  hipLaunchKernelGGL(fn, dim3(grid), dim3(kBlock), lds, (hipStream_t)stream, d_in, d_out,
                      (uint64_t)n, generations, plain < groups ? groups - plain : (uint64_t)0);
   return launched("k_step (order) launch");
 }
