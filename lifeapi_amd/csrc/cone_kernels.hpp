@@ -21,129 +21,26 @@
 // columns are exact.  A window with K >= 64 loads the whole board from
 // column 0, where the rotate is the true torus.
 //
-// The pass over a wave's universes (cone_wave) and the window tests
-// (cone_window, cone_whole, cone_fits) live in step_kernels.hpp, shared with
-// the iterated search loop's kContainsLo.  This file holds the kernels that
-// launch them: k_cone_adapt (shipped: the chunk of universes per wave chosen
-// from the window), k_cone (fixed shapes, the tuning build's A/Bs) and the
-// whole-board Contains pass with 16-byte loads.
+// The window tests (cone_window, cone_whole, cone_fits, cone_rows) are in
+// cone_window.hpp, the passes over a wave's universes (cone_wave and the
+// rest) in cone_passes.hpp, the window split layout in cone_split.hpp; all
+// are shared with the iterated search loop's k_step_contains_split
+// (contains_kernels.hpp).  This file holds the kernels that run them:
+// k_cone_adapt (shipped: the chunk of universes per wave chosen from the
+// window) and k_cone (fixed shapes, the tuning build's A/Bs), with their
+// launchers.
 #pragma once
 
 #include <type_traits>
 
-#include "step_kernels.hpp"
+#include "cone_passes.hpp"
+#include "cone_split.hpp"
+#include "host.hpp"
 
 namespace lifeapi_impl {
+// internal linkage: every library that includes this header gets its own
+// kernels (the product and the tuning build never share instantiations)
 namespace {
-
-// Contains over the whole board (K = 64) on a 16-byte aligned batch: lane l
-// reads words 2(l mod 32), 2(l mod 32) + 1 of universe 2k + l / 32 (one
-// dwordx4 moves two universes per wave-instruction, as k_contains16), RMAX
-// loads in flight per pass.
-template <int UPW, int RMAX>
-__device__ __forceinline__ void cone_wave_full16(const uint64_t *in, const uint64_t *__restrict__ wanted,
-                                                 const uint64_t *__restrict__ unwanted, uint8_t *__restrict__ out,
-                                                 uint64_t n, uint64_t u_first, uint64_t u_step, int lane) {
-  constexpr int RB = UPW / 2 < RMAX ? UPW / 2 : RMAX;
-  static_assert(UPW % (2 * RB) == 0, "passes of 2 RB universes");
-  const int half = lane >> 5, col = (lane & 31) * 2;
-  const uint64_t w0 = wanted[col], w1 = wanted[col + 1];
-  const uint64_t m0 = w0 | unwanted[col], m1 = w1 | unwanted[col + 1];
-  for (uint64_t u0 = u_first; u0 < n; u0 += u_step) {
-    uint32_t mine = 0;  // lane L: the answer for universe u0 + L
-#pragma unroll 1
-    for (int pass = 0; pass < UPW / (2 * RB); ++pass) {
-      const uint64_t ub = u0 + (uint64_t)pass * 2 * RB;
-      u64x2 v[RB];
-#pragma unroll
-      for (int k = 0; k < RB; ++k) {
-        const uint64_t u = ub + 2 * k + half;
-        v[k] = u < n ? __builtin_nontemporal_load(reinterpret_cast<const u64x2 *>(in + u * kWave + col))
-                     : u64x2{w0, w1};
-      }
-#pragma unroll
-      for (int k = 0; k < RB; ++k) {
-        const uint64_t d = ((v[k][0] ^ w0) & m0) | ((v[k][1] ^ w1) & m1);
-        const uint64_t bad = __ballot(d != 0ull);  // lanes 0-31: universe 2k, 32-63: 2k+1
-        const uint32_t rel = (uint32_t)lane - (uint32_t)(pass * 2 * RB + 2 * k);
-        if (rel < 2u) mine = (uint32_t)(bad >> (32 * rel)) == 0u ? 1u : 0u;
-      }
-    }
-    if (lane < UPW && u0 + lane < n) out[u0 + lane] = (uint8_t)mine;
-  }
-}
-
-// (dma_fetch_pass: cone_split.hpp)
-
-// The whole-board pass (K = 64) through LDS: each register set is one
-// universe, RB sets per pass; the RB universes of a pass (RB * 512
-// contiguous bytes) arrive by RB / 2 sixteen-byte-per-lane global_load_lds
-// (LDS-DMA, no VGPR destination: lanes 0-31 fill one universe, 32-63 the
-// next) and leave by ds_read_b64 with lane = column, and the next pass's are
-// fetched as soon as this pass has been read out, so that they stream in
-// while this pass steps.  Chunks of 2 RB universes per wave, u_step apart;
-// one coalesced store of answers per chunk.  `img`: this wave's RB * 512
-// bytes of LDS.  The batch must be 16-byte aligned.
-template <int RB, bool FIRST, typename OutT>
-__device__ __forceinline__ void cone_wave_full_dma(const uint64_t *in, uint64_t w64, uint64_t m64,
-                                                   OutT *__restrict__ out, uint64_t n, uint64_t u_first,
-                                                   uint64_t u_step, uint32_t gens, int lane, uint64_t *img,
-                                                   bool prefetched) {
-  static_assert(RB % 2 == 0 && 2 * RB <= kWave, "passes of pairs of universes, one answer per lane");
-  const W tw = split(w64), tm = split(m64);
-  auto clean = [&](W s) __attribute__((always_inline)) {
-    const uint32_t d = ((s.lo ^ tw.lo) & tm.lo) | ((s.hi ^ tw.hi) & tm.hi);
-    return __ballot(d != 0u) == 0ull;
-  };
-  // pass t: universes [base(t), base(t) + RB); chunk t / 2
-  auto base = [&](uint64_t t) { return u_first + (t >> 1) * u_step + (t & 1) * RB; };
-  auto fetch = [&](uint64_t ub) __attribute__((always_inline)) { dma_fetch_pass<RB>(in, n, ub, lane, img); };
-  if (u_first >= n) return;
-  if (!prefetched) fetch(u_first);  // (else the caller issued it)
-  uint32_t mine = 0;  // lane L: the answer for universe (chunk start) + L
-  int after = 0;      // vector-memory ops issued after the pending fetch (the chunk's answer store)
-  for (uint64_t t = 0;; ++t) {
-    const uint64_t ub = base(t);
-    if (ub >= n) break;
-    if (after) __builtin_amdgcn_s_waitcnt(kWaitVm1);
-    else __builtin_amdgcn_s_waitcnt(kWaitVm0);
-    W a[RB];
-#pragma unroll
-    for (int k = 0; k < RB; ++k) a[k] = split(img[k * kWave + lane]);
-    __builtin_amdgcn_s_waitcnt(kWaitLgkm0);  // read out before the next fetch lands
-    const uint64_t nb = base(t + 1);
-    if (nb < n) fetch(nb);
-    uint32_t res[RB];
-    if constexpr (FIRST) {
-#pragma unroll
-      for (int k = 0; k < RB; ++k) res[k] = 0;
-      for (uint32_t g = 1; g <= gens; ++g) {
-#pragma unroll
-        for (int k = 0; k < RB; ++k) {
-          a[k] = life_gen<XDPP, 3>(a[k], nullptr, lane);
-          if (res[k] == 0 && clean(a[k])) res[k] = g;
-        }
-      }
-    } else {
-#pragma unroll
-      for (int k = 0; k < RB; ++k) res[k] = clean(a[k]) ? 1u : 0u;
-    }
-#pragma unroll
-    for (int k = 0; k < RB; ++k)
-      if ((uint32_t)lane == (uint32_t)((t & 1) * RB + k)) mine = res[k];
-    after = 0;
-    if ((t & 1) || ub + RB >= n) {  // the chunk's last pass: store its answers
-      const uint64_t u0 = base(t & ~1ull);
-      if (lane < 2 * RB && u0 + lane < n) out[u0 + lane] = (OutT)mine;
-      mine = 0;
-      after = 1;
-    }
-  }
-}
-
-// (cone_wave_rows_dma: cone_split.hpp)
-
-// (cone_rows and kConeRowsWindowGens: step_kernels.hpp)
 
 // UPW universes per wave (one-shot grid of ceil(n / UPW) waves), every wave
 // choosing its lane layout from the window (wave-uniform: the target is the
@@ -365,12 +262,12 @@ constexpr int kConeAdaptBlocksPerCU = 16;
 // batch (1M universes: 16 and 32 within 1-3 % of each other on every
 // target, 8 up to 9 % slower on the one-row whole board; profiles/r06/ab/)
 constexpr int kFilterIterBlocksPerCU = 16;
-// (kConeWholeWinGens: step_kernels.hpp)
+// (kConeRowsWindowGens, kConeWholeWinGens: cone_window.hpp)
 // The iterated search loop (gens > 2, no final states) steps the light cone
 // while it spans at most this many columns (P <= 32 lanes per universe: at
 // most half the natural layout's work per universe-generation, against the
 // split layout's 18 issue slots plus its layout change) -- inside
-// kContainsLo (step_kernels.hpp, kConeLoUniverses = 8 universes per wave
+// kContainsLo (contains_kernels.hpp, kConeLoUniverses = 8 universes per wave
 // chunk: that work is VALU-bound, and 64 per wave would leave 64K universes
 // one wave per SIMD).
 constexpr uint32_t kConeIterColumns = 32;

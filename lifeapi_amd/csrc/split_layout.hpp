@@ -38,8 +38,7 @@ __device__ __forceinline__ W from_eo(W e) {
   return W{zip32(__builtin_amdgcn_perm(e.hi, e.lo, 0x05040100u)),
            zip32(__builtin_amdgcn_perm(e.hi, e.lo, 0x07060302u))};
 }
-__device__ __forceinline__ uint32_t rotl1(uint32_t x) { return __builtin_amdgcn_alignbit(x, x, 31); }
-__device__ __forceinline__ uint32_t rotr1(uint32_t x) { return __builtin_amdgcn_alignbit(x, x, 1); }
+// (rotl1, rotr1, the one rotate per plane: life_gen.hpp, RULE 4)
 
 // ------------------------------------------------------------------------
 // Row-split layouts (RULE 5: S = 4, RULE 6: S = 8, RULE 7: S = 16)

@@ -1,12 +1,15 @@
 // step.hip -- batched LifeState::Step() (LifeAPI.hpp:1196-1216, Stepped(n)
 // :877-886) and the fused Step + Contains (LifeTarget.hpp:44-51): the
 // shipped kernel configurations and their C ABI (include/lifeapi_hip.h).
-// The kernels are in step_kernels.hpp; the measured alternatives (other
+// The kernels are in step_kernels.hpp (Step), contains_kernels.hpp (Step +
+// Contains) and cone_kernels.hpp (the light-cone filter); the measured alternatives (other
 // networks, exchanges, layouts and schedules) live in the tuning build,
 // tools/tune/tune_step.hip, and are not part of this library.
 #include <algorithm>
 
 #include "cone_kernels.hpp"
+#include "contains_kernels.hpp"
+#include "step_kernels.hpp"
 
 using namespace lifeapi_impl;
 
@@ -162,7 +165,7 @@ int lifeapi_step_contains_batch_dev(const uint64_t *d_in, uint64_t *d_final,
     // the search filter proper (first hits only) at 1-2 generations: the
     // target's light cone, or the whole board, in the natural layout
     // (cone_kernels.hpp k_cone_adapt, DMA form): a whole-board target takes
-    // the universes through LDS (cone_wave_full_dma / cone_wave_rows_dma, 8
+    // the universes through LDS (cone_passes.hpp cone_wave_full_dma / cone_wave_rows_dma, 8
     // per pass by global_load_lds, the next pass fetched while this one
     // steps), every other window its cone (cone_wave); every wave decides,
     // on a grid of at most kConeAdaptBlocksPerCU blocks per CU looping over
@@ -180,7 +183,7 @@ int lifeapi_step_contains_batch_dev(const uint64_t *d_in, uint64_t *d_final,
   }
   if (!d_final) {
     // 3+ generations, first hits only (round 6): one launch of the merged
-    // split kernel (step_kernels.hpp k_step_contains_split, kContainsAll),
+    // split kernel (contains_kernels.hpp k_step_contains_split, kContainsAll),
     // whose waves take the pass their target calls for -- no report, so a
     // loop that rewrites its target buffers loses nothing:
     // * care rows that fit 32 with the light cone (cone_rows): on a whole
@@ -222,8 +225,8 @@ int lifeapi_step_contains_batch_dev(const uint64_t *d_in, uint64_t *d_final,
     const int split_cap = kSplitIterBlocksPerCU;
     const uint32_t cone_max = 0;  // (final states: every universe steps the whole board)
     // two kernels, one per register layout (a target window of <= 4 rows in
-    // 62 VGPRs, 8 waves per SIMD; the rest in 70, 7 waves): each wave finds
-    // the window and only the matching kernel works (step_kernels.hpp
+    // 62 VGPRs, 8 waves per SIMD; the rest in 71, 7 waves): each wave finds
+    // the window and only the matching kernel works (contains_kernels.hpp
     // kContainsLo / kContainsHi)
     using Fn = void (*)(const uint64_t *, uint64_t *, const uint64_t *, const uint64_t *, uint32_t *, uint64_t,
                         uint32_t, uint32_t);

@@ -1,4 +1,5 @@
-"""CPU: the light-cone kernels' data flow (lifeapi_amd/csrc/cone_kernels.hpp),
+"""CPU: the light-cone kernels' data flow (lifeapi_amd/csrc/cone_kernels.hpp,
+the passes in cone_passes.hpp, the window tests in cone_window.hpp),
 modelled lane for lane and checked against the oracle's direct answer.
 
 k_cone packs 64 / P universes into one 64-lane register set, lane j of group
@@ -11,7 +12,7 @@ the kernel's per-group test.  Agreement with Contains of the true state
 (LifeTarget.hpp:44-51) on every window shape is the light-cone argument,
 checked without a GPU: the neighbouring groups' columns that the rotate
 brings into a group's margins never reach its care columns within g
-generations.  The window search restates care_window (step_kernels.hpp).
+generations.  The window search restates care_window (device.hpp).
 """
 import numpy as np
 import pytest
@@ -20,7 +21,7 @@ M64 = (1 << 64) - 1
 
 
 def care_window(mask: int):
-    """(x0, w): step_kernels.hpp care_window -- the complement of the longest
+    """(x0, w): device.hpp care_window -- the complement of the longest
     cyclic run of empty positions, the lowest-starting run on ties; (0, 1)
     for an empty mask"""
     if mask == 0:
@@ -120,7 +121,7 @@ def rotr64(v: int, k: int) -> int:
 
 
 def cone_fits(mask: int, gens: int, kmax: int) -> bool:
-    """step_kernels.hpp cone_fits: a cyclic run of >= 64 - kmax + 2 gens empty
+    """cone_window.hpp cone_fits: a cyclic run of >= 64 - kmax + 2 gens empty
     columns, by doubling to runs of 32 and one shifted AND"""
     run = ~mask & M64
     for k in range(5):
@@ -129,7 +130,7 @@ def cone_fits(mask: int, gens: int, kmax: int) -> bool:
 
 
 def has_run(e: int, L: int) -> bool:
-    """step_kernels.hpp has_run: a cyclic run of >= L set bits in e"""
+    """cone_window.hpp has_run: a cyclic run of >= L set bits in e"""
     if L >= 64:
         return e == M64
     run = [e]

@@ -918,7 +918,7 @@ def _rows_target(rows, cols, wanted_at=None):
 ])
 def test_filter_whole_board_row_windows(hip, port, rows, gens_list):
     """A whole-board target whose care rows, widened by the light cone, fit 8,
-    16 or 32 rows takes the packed row-window pass (cone_kernels.hpp
+    16 or 32 rows takes the packed row-window pass (cone_passes.hpp
     cone_wave_rows_dma: 4, 2 or 1 universes per 32-bit register, shifts for
     the vertical neighbours) in the LDS form; windows across row 63 and across
     the 32-bit halves; every call against the oracle, three calls each

@@ -399,7 +399,7 @@ def test_iterated_search_loop_short_targets_vs_reference(hip, R, port, w, h, gen
     layout (cone_split.hpp; the round-6 shapes cover P = 8 / 16 / 32 / 64
     lanes x R = 32 / 16 rows), narrower cones of taller targets the natural
     layout's cone pass, the rest the 8-way row split that their height
-    picks (step_kernels.hpp kContainsAll).  Against the reference's Step() +
+    picks (contains_kernels.hpp kContainsAll).  Against the reference's Step() +
     Contains loop."""
     rng = np.random.default_rng(100 * w + 10 * h + gens)
     n = 777

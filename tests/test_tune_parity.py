@@ -95,7 +95,7 @@ def test_bad_cfgs_rejected(tune, hip):
 @pytest.mark.parametrize("gens", [3, 6, 8, 9, 37])
 @pytest.mark.parametrize("with_final", [False, True])
 def test_step_contains_variants(tune, port, variant, gens, with_final):
-    """The fused Step + Contains kernels of the tuning build (step_kernels.hpp
+    """The fused Step + Contains kernels of the tuning build (contains_kernels.hpp
     kContainsAsm: 0 compiled loop ... 7 batched, low layout) against the
     oracle's step-then-Contains loop (LifeTarget.hpp:44-51), ragged n,
     planted hits; gens 3 / 6 / 8 / 9 / 37 = 0 / 0 / 1 / 1 / 4 blocks of

@@ -20,9 +20,9 @@ MUTANTS = {
     "B": ("cone_split.hpp", "e[u] = cut(img[u * kWave + lane]);",
           "e[u] = cut(img[(u ^ 1) * kWave + lane]);"),
     # the packed row window starts one row late
-    "C": ("step_kernels.hpp", "  y0 = (cy0 - gens) & 63u;", "  y0 = (cy0 - gens + 1u) & 63u;"),
+    "C": ("cone_window.hpp","  y0 = (cy0 - gens) & 63u;", "  y0 = (cy0 - gens + 1u) & 63u;"),
     # the column light cone one column narrower on each side
-    "D": ("step_kernels.hpp",
+    "D": ("cone_window.hpp",
           "K = gens >= (uint32_t)kWave / 2 ? (uint32_t)kWave : w + 2 * gens;\n  xs = (x0 - gens) & (kWave - 1);",
           "K = gens >= (uint32_t)kWave / 2 ? (uint32_t)kWave : w + 2 * gens - 2;\n  xs = (x0 - gens + 1) & (kWave - 1);"),
 }

@@ -982,7 +982,8 @@ PRODUCT_BATCH_H = range(LOW_H + 1, BATCH_MAX_H + 1)
 
 def _ablation_decls():
     """forward declarations of the tuning build's loops: step_kernels.hpp
-    names them in template branches the product never instantiates"""
+    (k_step_split) and contains_kernels.hpp (k_step_contains_split) name them
+    in template branches the product never instantiates"""
     names = [(f"split_gens_asm_v{k}", _SIG_LOOP) for k in range(1, len(VARIANTS))]
     names += [("split_gens_asm2", _SIG_TWO), ("split_contains_asm", _SIG_CONT)]
     names += [(f"split_contains_asm_lean_h{h}", _SIG_CONT) for h in range(1, S)]

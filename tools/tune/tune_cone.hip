@@ -3,6 +3,7 @@
 // computes the same answers as the shipped one.
 #include "lifeapi_tune.h"
 #include "cone_kernels.hpp"
+#include "contains_kernels.hpp"
 
 using namespace lifeapi_impl;
 
@@ -178,7 +179,7 @@ int lifeapi_tune_cone(int first, const uint64_t *d_in, const uint64_t *d_wanted,
  * columns, grid capped at cone_cap blocks per CU, 0 = one-shot), then the
  * split pair (kContainsLo, kContainsHi) with each grid capped at split_cap
  * blocks per CU (0 = one-shot) -- whose kContainsLo now also steps the cone
- * (step_kernels.hpp), so the cone launch's waves have answered first and
+ * (contains_kernels.hpp), so the cone launch's waves have answered first and
  * Lo's rewrite the same values.  cone_cap < 0: no cone launch (the shipped
  * form, step.hip).                                                          */
 int lifeapi_tune_search_iter(const uint64_t *d_in, const uint64_t *d_wanted, const uint64_t *d_unwanted,

@@ -9,6 +9,7 @@
 #include <algorithm>
 
 #include "lifeapi_tune.h"
+#include "contains_kernels.hpp"
 #include "step_kernels.hpp"
 #include "step_r6.hpp"
 #include "split_asm_tune.inc"
@@ -526,7 +527,7 @@ __global__ __launch_bounds__(kBlock) void k_step_pair(const uint64_t *in, uint64
 
 extern "C" {
 
-/* fused Step + Contains on the split layout: variant = step_kernels.hpp's
+/* fused Step + Contains on the split layout: variant = contains_kernels.hpp's
  * ASM (0 compiled loop ... 7 / 8 the shipped pair's halves) */
 int lifeapi_tune_step_contains(const uint64_t *d_in, uint64_t *d_final, const uint64_t *d_wanted,
                                const uint64_t *d_unwanted, uint32_t *d_first_gen, size_t n, uint32_t generations,
