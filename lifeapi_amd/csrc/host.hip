@@ -196,8 +196,7 @@ int check_batch(const void *in, const void *out, size_t n) {
   if (!in || !out) return fail(LIFEAPI_E_INVALID, "null universe pointer%s");
   if (!aligned8(in) || !aligned8(out)) return fail(LIFEAPI_E_INVALID, "universe pointers must be 8-byte aligned%s");
   if (n > (SIZE_MAX / 512)) return fail(LIFEAPI_E_INVALID, "n too large%s");
-  const uintptr_t a = (uintptr_t)in, b = (uintptr_t)out, bytes = (uintptr_t)n * 512u;
-  if (a != b && a < b + bytes && b < a + bytes)
+  if (in != out && ranges_overlap(in, n * 512, out, n * 512))
     return fail(LIFEAPI_E_INVALID, "input and output batches overlap (only in == out is allowed)%s");
   return LIFEAPI_OK;
 }
@@ -228,14 +227,19 @@ int launched(const char *what) {
 // under 1 ms and takes 1M universes from 19.4 to 12.2-13.1 ms
 // (profiles/r01/host_bench.jsonl).  Arrays the caller pinned already
 // (lifeapi_host_register) or that cannot be pinned are used as they are.
+// An array that is not per-universe data (HostIO::whole: the 512-byte halves
+// of a Contains target) has a slot of its own in each lane's buffer and is
+// copied in again ahead of every chunk's launch, on the chunk's stream: the
+// call owns no other device memory, and stream order is all that keeps a
+// launch behind its target.
 constexpr int kLanes = 2;  // (the event chain below assumes two)
 constexpr size_t kChunkBytes = size_t(64) << 20;  // staging per stream and pass
 constexpr size_t kPinMinBytes = size_t(8) << 20;  // smaller calls stay pageable
 
 // Ranges this library pinned, shared by every call in the process: a call
 // whose array lies inside one takes a reference instead of registering again,
-// so concurrent calls (other threads, the per-device shards of
-// lifeapi_step_batch) never unpin memory another call is still copying.
+// so concurrent calls (other threads, the per-device shards of a device = -1
+// call) never unpin memory another call is still copying.
 struct PinRec {
   uintptr_t lo, hi;
   int refs;
@@ -319,10 +323,10 @@ HostCtx *ctx_for(int dev) {
   return g_ctx[dev];
 }
 
-// Chunks are disjoint ranges of every array, so in-place arrays (src == dst)
-// are safe.
-int host_chunked(int dev, size_t n, const HostIO *io, int nio, ChunkFn fn, const void *arg) {
-  if (nio > 8) return fail(LIFEAPI_E_INVALID, "too many arrays%s");
+// n universes of io[0..nio) (nio <= kMaxHostArrays: host_batch) on device
+// dev.  Chunks are disjoint ranges of every per-universe array, so in-place
+// arrays (src == dst) are safe.
+static int host_chunked(int dev, size_t n, const HostIO *io, size_t nio, const ChunkFn &fn) {
   DeviceGuard guard;
   hipError_t e = hipSetDevice(dev);
   if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
@@ -335,12 +339,13 @@ int host_chunked(int dev, size_t n, const HostIO *io, int nio, ChunkFn fn, const
       e = hipEventCreateWithFlags(&c->h2d_done[l], hipEventDisableTiming);
       if (e != hipSuccess) return fail_hip(e, "hipEventCreate");
     }
-  size_t per = 0;
-  for (int k = 0; k < nio; ++k) per += (io[k].bytes + 255) & ~size_t(255);
+  size_t per = 0;  // (whole arrays do not move the chunk boundaries)
+  for (size_t k = 0; k < nio; ++k)
+    if (!io[k].whole) per += (io[k].bytes + 255) & ~size_t(255);
   const size_t half = (n + kLanes - 1) / kLanes;
   const size_t chunk = std::max<size_t>(1, std::min(half, kChunkBytes / per));
   size_t need = 0;
-  for (int k = 0; k < nio; ++k) need += ((io[k].bytes * chunk + 255) & ~size_t(255));
+  for (size_t k = 0; k < nio; ++k) need += (io[k].span(chunk) + 255) & ~size_t(255);
   if (c->cap < need) {
     for (int l = 0; l < kLanes; ++l) {
       if (c->buf[l]) (void)hipFree(c->buf[l]);
@@ -355,12 +360,12 @@ int host_chunked(int dev, size_t n, const HostIO *io, int nio, ChunkFn fn, const
   }
   // page-lock the caller's arrays for this call (see above)
   CallPins pins;
-  for (int q = 0; q < nio; ++q) {
-    pins.add(io[q].src, n * io[q].bytes);
-    if (io[q].dst != io[q].src) pins.add(io[q].dst, n * io[q].bytes);
+  for (size_t q = 0; q < nio; ++q) {
+    pins.add(io[q].src, io[q].span(n));
+    if (io[q].dst != io[q].src) pins.add(io[q].dst, io[q].span(n));
   }
   int rc = LIFEAPI_OK;
-  void *d[8];
+  void *d[kMaxHostArrays];
   for (size_t k = 0; k * chunk < n && rc == LIFEAPI_OK; ++k) {
     const int l = (int)(k % kLanes);
     hipStream_t st = c->stream[l];
@@ -370,19 +375,19 @@ int host_chunked(int dev, size_t n, const HostIO *io, int nio, ChunkFn fn, const
       break;
     }
     size_t pos = 0;
-    for (int q = 0; q < nio && rc == LIFEAPI_OK; ++q) {
+    for (size_t q = 0; q < nio && rc == LIFEAPI_OK; ++q) {
       d[q] = c->buf[l] + pos;
-      pos += (io[q].bytes * chunk + 255) & ~size_t(255);
-      if (io[q].src &&
-          (e = hipMemcpyAsync(d[q], (const char *)io[q].src + off * io[q].bytes, m * io[q].bytes,
-                              hipMemcpyHostToDevice, st)) != hipSuccess)
+      pos += (io[q].span(chunk) + 255) & ~size_t(255);
+      const size_t at = io[q].whole ? 0 : off * io[q].bytes;
+      if (io[q].src && (e = hipMemcpyAsync(d[q], (const char *)io[q].src + at, io[q].span(m),
+                                           hipMemcpyHostToDevice, st)) != hipSuccess)
         rc = fail_hip(e, "hipMemcpyAsync(H2D)");
     }
     if (rc == LIFEAPI_OK && (e = hipEventRecord(c->h2d_done[l], st)) != hipSuccess)
       rc = fail_hip(e, "hipEventRecord");
-    if (rc == LIFEAPI_OK) rc = fn(d, m, st, arg);
-    for (int q = 0; q < nio && rc == LIFEAPI_OK; ++q)
-      if (io[q].dst &&
+    if (rc == LIFEAPI_OK) rc = fn(d, m, st);
+    for (size_t q = 0; q < nio && rc == LIFEAPI_OK; ++q)
+      if (io[q].dst && !io[q].whole &&
           (e = hipMemcpyAsync((char *)io[q].dst + off * io[q].bytes, d[q], m * io[q].bytes,
                               hipMemcpyDeviceToHost, st)) != hipSuccess)
         rc = fail_hip(e, "hipMemcpyAsync(D2H)");
@@ -406,7 +411,7 @@ int host_device(int device) {
 
 // device >= 0: fn(0, n, device) on that device.  device -1: one contiguous
 // shard per visible device, fn(lo, hi, dev) on one host thread each, with the
-// given host ranges page-locked once for all shards (shard boundaries share
+// host arrays page-locked once for all shards (shard boundaries share
 // pages).  LIFEAPI_HOST_SHARDS=k (1 <= k <= 64, else LIFEAPI_E_INVALID; empty = unset)
 // overrides the shard count (at most n shards), shard s
 // running on device s mod ndev: a rehearsal knob that runs the threaded path
@@ -414,7 +419,7 @@ int host_device(int device) {
 // failing shard's code and message are returned.
 constexpr long kMaxHostShards = 64;
 template <class F>
-int over_devices(size_t n, int device, const std::pair<const void *, size_t> *ranges, int nranges, F &&fn) {
+static int over_devices(size_t n, int device, std::initializer_list<HostIO> io, F &&fn) {
   const int ndev = lifeapi_device_count();
   if (ndev <= 0) return fail(LIFEAPI_E_NODEVICE, "no HIP device visible%s");
   if (device >= ndev || device < -1) return fail(LIFEAPI_E_NODEVICE, "bad device index%s");
@@ -432,8 +437,10 @@ int over_devices(size_t n, int device, const std::pair<const void *, size_t> *ra
   }
   if (device >= 0 || shards == 1) return fn(0, n, device < 0 ? 0 : device);
   CallPins pins;
-  for (int r = 0; r < nranges; ++r)
-    if (ranges[r].first) pins.add(ranges[r].first, ranges[r].second);
+  for (const HostIO &a : io) {
+    pins.add(a.src, a.span(n));
+    if (a.dst != a.src) pins.add(a.dst, a.span(n));
+  }
   std::vector<int> rcs(shards, LIFEAPI_OK);
   std::vector<std::string> errs(shards);
   std::vector<std::thread> pool;
@@ -454,31 +461,20 @@ int over_devices(size_t n, int device, const std::pair<const void *, size_t> *ra
 }
 
 // host_chunked over device(s): device >= 0 one device, -1 every visible one
-// (over_devices), each shard's arrays offset by its first universe
-int host_batch(size_t n, int device, const HostIO *io, int nio, ChunkFn fn, const void *arg) {
-  std::pair<const void *, size_t> ranges[8];
-  int nr = 0;
-  for (int i = 0; i < nio && nr < 7; ++i) {
-    if (io[i].src) ranges[nr++] = {io[i].src, n * io[i].bytes};
-    if (io[i].dst && io[i].dst != io[i].src) ranges[nr++] = {io[i].dst, n * io[i].bytes};
-  }
-  return over_devices(n, device, ranges, nr, [&](size_t lo, size_t hi, int dev) {
-    HostIO sh[4];
-    for (int i = 0; i < nio; ++i)
-      sh[i] = {io[i].src ? (const char *)io[i].src + lo * io[i].bytes : nullptr,
-               io[i].dst ? (char *)io[i].dst + lo * io[i].bytes : nullptr, io[i].bytes};
-    return host_chunked(dev, hi - lo, sh, nio, fn, arg);
+// (over_devices), each shard's per-universe arrays offset by its first
+// universe, whole arrays as they are
+int host_batch(size_t n, int device, std::initializer_list<HostIO> io, const ChunkFn &fn) {
+  if (io.size() > kMaxHostArrays) return fail(LIFEAPI_E_INVALID, "too many arrays%s");
+  return over_devices(n, device, io, [&](size_t lo, size_t hi, int dev) {
+    HostIO sh[kMaxHostArrays];
+    size_t k = 0;
+    for (HostIO a : io) {
+      if (a.src && !a.whole) a.src = (const char *)a.src + lo * a.bytes;
+      if (a.dst && !a.whole) a.dst = (char *)a.dst + lo * a.bytes;
+      sh[k++] = a;
+    }
+    return host_chunked(dev, hi - lo, sh, k, fn);
   });
-}
-
-int host_step_one_device(const uint64_t *in, uint64_t *out, size_t n, uint32_t gens, int dev) {
-  const HostIO io[1] = {{in, out, 512}};
-  return host_chunked(dev, n, io, 1,
-                      [](void *const *d, size_t m, hipStream_t s, const void *arg) {
-                        return lifeapi_step_batch_dev((const uint64_t *)d[0], (uint64_t *)d[0], m,
-                                                      *(const uint32_t *)arg, s);
-                      },
-                      &gens);
 }
 
 }  // namespace lifeapi_impl
@@ -501,9 +497,8 @@ int lifeapi_step_batch(const uint64_t *in, uint64_t *out, size_t n, uint32_t gen
                        int device) {
   int rc = check_batch(in, out, n);
   if (rc != LIFEAPI_OK || n == 0) return rc;
-  const std::pair<const void *, size_t> ranges[2] = {{in, n * 512}, {out != in ? out : nullptr, n * 512}};
-  return over_devices(n, device, ranges, 2, [&](size_t lo, size_t hi, int dev) {
-    return host_step_one_device(in + lo * 64, out + lo * 64, hi - lo, generations, dev);
+  return host_batch(n, device, {{in, out, 512}}, [=](void *const *d, size_t m, hipStream_t s) {
+    return lifeapi_step_batch_dev((const uint64_t *)d[0], (uint64_t *)d[0], m, generations, s);
   });
 }
 
@@ -524,23 +519,18 @@ int lifeapi_host_unregister(void *p) {
 int lifeapi_pop_batch(const uint64_t *states, uint32_t *pop, size_t n, int device) {
   if (n == 0) return LIFEAPI_OK;
   if (!states || !pop || !aligned8(states)) return fail(LIFEAPI_E_INVALID, "bad pointer to lifeapi_pop_batch%s");
-  const HostIO io[2] = {{states, nullptr, 512}, {nullptr, pop, 4}};
-  return host_batch(n, device, io, 2,
-                      [](void *const *d, size_t m, hipStream_t s, const void *) {
-                        return lifeapi_pop_batch_dev((const uint64_t *)d[0], (uint32_t *)d[1], m, s);
-                      },
-                      nullptr);
+  return host_batch(n, device, {{states, nullptr, 512}, {nullptr, pop, 4}},
+                    [](void *const *d, size_t m, hipStream_t s) {
+                      return lifeapi_pop_batch_dev((const uint64_t *)d[0], (uint32_t *)d[1], m, s);
+                    });
 }
 
 int lifeapi_weld_step_batch(uint64_t *welds, size_t n, uint32_t generations, int device) {
   if (n == 0) return LIFEAPI_OK;
   if (!welds || !aligned8(welds)) return fail(LIFEAPI_E_INVALID, "bad pointer to lifeapi_weld_step_batch%s");
-  const HostIO io[1] = {{welds, welds, 4 * 512}};
-  return host_batch(n, device, io, 1,
-                      [](void *const *d, size_t m, hipStream_t s, const void *arg) {
-                        return lifeapi_weld_step_batch_dev((uint64_t *)d[0], m, *(const uint32_t *)arg, s);
-                      },
-                      &generations);
+  return host_batch(n, device, {{welds, welds, 4 * 512}}, [=](void *const *d, size_t m, hipStream_t s) {
+    return lifeapi_weld_step_batch_dev((uint64_t *)d[0], m, generations, s);
+  });
 }
 
 int lifeapi_stable_pass_batch(uint64_t *planes, uint8_t *flags, size_t n, int pass,
@@ -548,40 +538,31 @@ int lifeapi_stable_pass_batch(uint64_t *planes, uint8_t *flags, size_t n, int pa
   if (n == 0) return LIFEAPI_OK;
   if (!planes || !flags || !aligned8(planes) || pass < 0 || pass > 5)
     return fail(LIFEAPI_E_INVALID, "bad argument to lifeapi_stable_pass_batch%s");
-  const uint32_t arg[2] = {(uint32_t)pass, max_iters};
-  const HostIO io[2] = {{planes, planes, 10 * 512}, {nullptr, flags, 1}};
-  return host_batch(n, device, io, 2,
-                      [](void *const *d, size_t m, hipStream_t s, const void *a) {
-                        const uint32_t *p = (const uint32_t *)a;
-                        return lifeapi_stable_pass_batch_dev((uint64_t *)d[0], (uint8_t *)d[1], m,
-                                                             (int)p[0], p[1], s);
-                      },
-                      arg);
+  return host_batch(n, device, {{planes, planes, 10 * 512}, {nullptr, flags, 1}},
+                    [=](void *const *d, size_t m, hipStream_t s) {
+                      return lifeapi_stable_pass_batch_dev((uint64_t *)d[0], (uint8_t *)d[1], m, pass,
+                                                           max_iters, s);
+                    });
 }
 
 int lifeapi_stable_vulnerable_batch(const uint64_t *planes, uint64_t *out, size_t n, int device) {
   if (n == 0) return LIFEAPI_OK;
   if (!planes || !out || !aligned8(planes) || !aligned8(out))
     return fail(LIFEAPI_E_INVALID, "bad pointer to lifeapi_stable_vulnerable_batch%s");
-  const HostIO io[2] = {{planes, nullptr, 10 * 512}, {nullptr, out, 512}};
-  return host_batch(n, device, io, 2,
-                      [](void *const *d, size_t m, hipStream_t s, const void *) {
-                        return lifeapi_stable_vulnerable_batch_dev((const uint64_t *)d[0], (uint64_t *)d[1],
-                                                                   m, s);
-                      },
-                      nullptr);
+  return host_batch(n, device, {{planes, nullptr, 10 * 512}, {nullptr, out, 512}},
+                    [](void *const *d, size_t m, hipStream_t s) {
+                      return lifeapi_stable_vulnerable_batch_dev((const uint64_t *)d[0], (uint64_t *)d[1], m, s);
+                    });
 }
 
 int lifeapi_neighbour_count_batch(const uint64_t *in, uint64_t *out, size_t n, int device) {
   if (n == 0) return LIFEAPI_OK;
   if (!in || !out || !aligned8(in) || !aligned8(out))
     return fail(LIFEAPI_E_INVALID, "bad pointer to lifeapi_neighbour_count_batch%s");
-  const HostIO io[2] = {{in, nullptr, 512}, {nullptr, out, 4 * 512}};
-  return host_batch(n, device, io, 2,
-                      [](void *const *d, size_t m, hipStream_t s, const void *) {
-                        return lifeapi_neighbour_count_batch_dev((const uint64_t *)d[0], (uint64_t *)d[1], m, s);
-                      },
-                      nullptr);
+  return host_batch(n, device, {{in, nullptr, 512}, {nullptr, out, 4 * 512}},
+                    [](void *const *d, size_t m, hipStream_t s) {
+                      return lifeapi_neighbour_count_batch_dev((const uint64_t *)d[0], (uint64_t *)d[1], m, s);
+                    });
 }
 
 int lifeapi_interaction_counts_batch(const uint64_t *in, uint64_t *out, size_t n, int with_next,
@@ -589,51 +570,21 @@ int lifeapi_interaction_counts_batch(const uint64_t *in, uint64_t *out, size_t n
   if (n == 0) return LIFEAPI_OK;
   if (!in || !out || !aligned8(in) || !aligned8(out))
     return fail(LIFEAPI_E_INVALID, "bad pointer to lifeapi_interaction_counts_batch%s");
-  const HostIO io[2] = {{in, nullptr, 512}, {nullptr, out, (with_next ? 4u : 3u) * 512}};
-  return host_batch(n, device, io, 2,
-                      [](void *const *d, size_t m, hipStream_t s, const void *a) {
-                        return lifeapi_interaction_counts_batch_dev((const uint64_t *)d[0], (uint64_t *)d[1],
-                                                                    m, *(const int *)a, s);
-                      },
-                      &with_next);
+  return host_batch(n, device, {{in, nullptr, 512}, {nullptr, out, (with_next ? 4u : 3u) * 512}},
+                    [=](void *const *d, size_t m, hipStream_t s) {
+                      return lifeapi_interaction_counts_batch_dev((const uint64_t *)d[0], (uint64_t *)d[1], m,
+                                                                  with_next, s);
+                    });
 }
 
 int lifeapi_refined_step_batch(const uint64_t *in, uint64_t *out, size_t n, int device) {
   if (n == 0) return LIFEAPI_OK;
   if (!in || !out || !aligned8(in) || !aligned8(out))
     return fail(LIFEAPI_E_INVALID, "bad pointer to lifeapi_refined_step_batch%s");
-  const HostIO io[2] = {{in, nullptr, 11 * 512}, {nullptr, out, 3 * 512}};
-  return host_batch(n, device, io, 2,
-                      [](void *const *d, size_t m, hipStream_t s, const void *) {
-                        return lifeapi_refined_step_batch_dev((const uint64_t *)d[0], (uint64_t *)d[1], m, s);
-                      },
-                      nullptr);
-}
-
-static int host_contains_one_device(const uint64_t *states, const uint64_t *wanted, const uint64_t *unwanted,
-                                    uint8_t *out, size_t n, int dev) {
-  // the target rides along as a tiny device copy owned by this call
-  DeviceGuard guard;
-  hipError_t e = hipSetDevice(dev);
-  if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
-  uint64_t *dt = nullptr;
-  if ((e = hipMalloc(&dt, 2 * 512)) != hipSuccess) return fail_hip(e, "hipMalloc(target)");
-  int rc = LIFEAPI_OK;
-  if ((e = hipMemcpy(dt, wanted, 512, hipMemcpyHostToDevice)) != hipSuccess ||
-      (e = hipMemcpy(dt + 64, unwanted, 512, hipMemcpyHostToDevice)) != hipSuccess)
-    rc = fail_hip(e, "hipMemcpy(target)");
-  if (rc == LIFEAPI_OK) {
-    const HostIO io[2] = {{states, nullptr, 512}, {nullptr, out, 1}};
-    rc = host_chunked(dev, n, io, 2,
-                      [](void *const *d, size_t m, hipStream_t s, const void *a) {
-                        const uint64_t *t = (const uint64_t *)a;
-                        return lifeapi_contains_batch_dev((const uint64_t *)d[0], t, t + 64,
-                                                          (uint8_t *)d[1], m, s);
-                      },
-                      dt);
-  }
-  (void)hipFree(dt);
-  return rc;
+  return host_batch(n, device, {{in, nullptr, 11 * 512}, {nullptr, out, 3 * 512}},
+                    [](void *const *d, size_t m, hipStream_t s) {
+                      return lifeapi_refined_step_batch_dev((const uint64_t *)d[0], (uint64_t *)d[1], m, s);
+                    });
 }
 
 int lifeapi_contains_batch(const uint64_t *states, const uint64_t *wanted, const uint64_t *unwanted,
@@ -641,44 +592,13 @@ int lifeapi_contains_batch(const uint64_t *states, const uint64_t *wanted, const
   if (n == 0) return LIFEAPI_OK;
   if (!states || !wanted || !unwanted || !out || !aligned8(states))
     return fail(LIFEAPI_E_INVALID, "bad pointer to lifeapi_contains_batch%s");
-  const std::pair<const void *, size_t> ranges[2] = {{states, n * 512}, {out, n}};
-  return over_devices(n, device, ranges, 2, [&](size_t lo, size_t hi, int dev) {
-    return host_contains_one_device(states + lo * 64, wanted, unwanted, out + lo, hi - lo, dev);
-  });
-}
-
-static int host_step_contains_one_device(const uint64_t *in, uint64_t *final_states, const uint64_t *wanted,
-                                         const uint64_t *unwanted, uint32_t *first_gen, size_t n,
-                                         uint32_t generations, int dev) {
-  DeviceGuard guard;
-  hipError_t e = hipSetDevice(dev);
-  if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
-  uint64_t *dt = nullptr;  // the target, a tiny device copy owned by this call
-  if ((e = hipMalloc(&dt, 2 * 512)) != hipSuccess) return fail_hip(e, "hipMalloc(target)");
-  int rc = LIFEAPI_OK;
-  if ((e = hipMemcpy(dt, wanted, 512, hipMemcpyHostToDevice)) != hipSuccess ||
-      (e = hipMemcpy(dt + 64, unwanted, 512, hipMemcpyHostToDevice)) != hipSuccess)
-    rc = fail_hip(e, "hipMemcpy(target)");
-  if (rc == LIFEAPI_OK) {
-    struct Arg {
-      const uint64_t *t;
-      uint32_t gens;
-      bool keep;
-    } arg{dt, generations, final_states != nullptr};
-    // the states' staging slot doubles as the device final buffer (in place)
-    const HostIO io[2] = {{in, final_states, 512}, {nullptr, first_gen, 4}};
-    rc = host_chunked(dev, n, io, 2,
-                      [](void *const *d, size_t m, hipStream_t s, const void *a) {
-                        const Arg *g = (const Arg *)a;
-                        return lifeapi_step_contains_batch_dev((const uint64_t *)d[0],
-                                                               g->keep ? (uint64_t *)d[0] : nullptr,
-                                                               g->t, g->t + 64, (uint32_t *)d[1], m,
-                                                               g->gens, s);
-                      },
-                      &arg);
-  }
-  (void)hipFree(dt);
-  return rc;
+  return host_batch(n, device,
+                    {{states, nullptr, 512}, {nullptr, out, 1}, {wanted, nullptr, 512, true},
+                     {unwanted, nullptr, 512, true}},
+                    [](void *const *d, size_t m, hipStream_t s) {
+                      return lifeapi_contains_batch_dev((const uint64_t *)d[0], (const uint64_t *)d[2],
+                                                        (const uint64_t *)d[3], (uint8_t *)d[1], m, s);
+                    });
 }
 
 int lifeapi_step_contains_batch(const uint64_t *in, uint64_t *final_states, const uint64_t *wanted,
@@ -691,12 +611,16 @@ int lifeapi_step_contains_batch(const uint64_t *in, uint64_t *final_states, cons
     const int rc = check_batch(in, final_states, n);
     if (rc != LIFEAPI_OK) return rc;
   }
-  const std::pair<const void *, size_t> ranges[3] = {
-      {in, n * 512}, {final_states != in ? final_states : nullptr, n * 512}, {first_gen, n * 4}};
-  return over_devices(n, device, ranges, 3, [&](size_t lo, size_t hi, int dev) {
-    return host_step_contains_one_device(in + lo * 64, final_states ? final_states + lo * 64 : nullptr, wanted,
-                                         unwanted, first_gen + lo, hi - lo, generations, dev);
-  });
+  // the states' staging slot doubles as the device final buffer (in place)
+  const bool keep = final_states != nullptr;
+  return host_batch(n, device,
+                    {{in, final_states, 512}, {nullptr, first_gen, 4}, {wanted, nullptr, 512, true},
+                     {unwanted, nullptr, 512, true}},
+                    [=](void *const *d, size_t m, hipStream_t s) {
+                      return lifeapi_step_contains_batch_dev(
+                          (const uint64_t *)d[0], keep ? (uint64_t *)d[0] : nullptr, (const uint64_t *)d[2],
+                          (const uint64_t *)d[3], (uint32_t *)d[1], m, generations, s);
+                    });
 }
 
 }  // extern "C"

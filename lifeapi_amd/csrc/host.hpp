@@ -5,6 +5,8 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <functional>
+#include <initializer_list>
 #include <string>
 
 #include "common.hpp"
@@ -38,6 +40,10 @@ bool launch_reverse(const void *d_in, const void *d_out, uint64_t bytes);
 void note_forward_write(const void *d_out, uint64_t bytes);
 bool aligned8(const void *p);
 inline bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
+// [a, a + abytes) and [b, b + bbytes) share a byte
+inline bool ranges_overlap(const void *a, size_t abytes, const void *b, size_t bbytes) {
+  return (uintptr_t)a < (uintptr_t)b + bbytes && (uintptr_t)b < (uintptr_t)a + abytes;
+}
 // n universes in / out: non-null, 8-byte aligned, equal or disjoint
 int check_batch(const void *in, const void *out, size_t n);
 // blocks for `waves_needed` waves, capped at cus * blocks_per_cu (0 = no cap)
@@ -55,18 +61,26 @@ struct DeviceGuard {  // restores the caller's current device
 
 // One host array taking part in a host-pointer call: `bytes` per universe;
 // src -> copied in before each chunk's launch, dst -> copied out after it
-// (src == dst for in-place arrays).
+// (src == dst for in-place arrays).  whole: `bytes` in all, the same for
+// every universe (a target): all of it is copied in before every chunk's
+// launch, to a 256-byte-aligned device address; never a dst.
 struct HostIO {
   const void *src;
   void *dst;
   size_t bytes;
+  bool whole = false;
+  size_t span(size_t m) const { return whole ? bytes : m * bytes; }  // bytes holding m universes
 };
-using ChunkFn = int (*)(void *const *dev, size_t m, hipStream_t s, const void *arg);
+constexpr size_t kMaxHostArrays = 8;  // per call
+// the stream-ordered *_dev call on one staged chunk: dev[k] is the device
+// copy of array k, m the chunk's universes
+using ChunkFn = std::function<int(void *const *dev, size_t m, hipStream_t s)>;
 
-// Stages n universes through this device's reusable buffers in chunks that
-// alternate between two streams: H2D, the stream-ordered *_dev entry point,
-// D2H, all asynchronous, then one sync of both streams.
-int host_chunked(int dev, size_t n, const HostIO *io, int nio, ChunkFn fn, const void *arg);
+// Stages n universes through each device's reusable buffers in chunks that
+// alternate between two streams: H2D, fn, D2H, all asynchronous, then one
+// sync of both streams.  device >= 0: that device; -1: one contiguous shard
+// per visible device, each on its own host thread (host.hip over_devices).
+int host_batch(size_t n, int device, std::initializer_list<HostIO> io, const ChunkFn &fn);
 // the device a host-pointer call runs on (-1 = device 0), or an error code
 int host_device(int device);
 

@@ -271,12 +271,10 @@ int lifeapi_rle_batch(const uint64_t *states, size_t n, char *text, size_t text_
   const int dev = host_device(device);
   if (dev < 0) return dev;
   std::vector<uint32_t> len(n);
-  const HostIO io[2] = {{states, nullptr, 512}, {nullptr, len.data(), 4}};
-  int rc = host_chunked(dev, n, io, 2,
-                        [](void *const *d, size_t m, hipStream_t s, const void *) {
-                          return lifeapi_rle_lengths_batch_dev((const uint64_t *)d[0], (uint32_t *)d[1], m, s);
-                        },
-                        nullptr);
+  int rc = host_batch(n, dev, {{states, nullptr, 512}, {nullptr, len.data(), 4}},
+                      [](void *const *d, size_t m, hipStream_t s) {
+                        return lifeapi_rle_lengths_batch_dev((const uint64_t *)d[0], (uint32_t *)d[1], m, s);
+                      });
   if (rc != LIFEAPI_OK) return rc;
   for (size_t u = 0; u < n; ++u) offsets[u + 1] = offsets[u] + len[u];
   if (!text) return LIFEAPI_OK;  // size query

@@ -33,8 +33,7 @@ static int counts_launch(const uint64_t *d_in, uint64_t *d_out, size_t n, int mo
   if (!d_in || !d_out || !aligned8(d_in) || !aligned8(d_out))
     return fail(LIFEAPI_E_INVALID, "bad pointer to a neighbourhood-count entry point%s");
   const size_t planes = mode == 1 ? 3 : 4;
-  const uintptr_t a = (uintptr_t)d_in, b = (uintptr_t)d_out;
-  if (a < b + n * planes * 512 && b < a + n * 512)
+  if (ranges_overlap(d_in, n * 512, d_out, n * planes * 512))
     return fail(LIFEAPI_E_INVALID, "count input and output overlap%s");
   int cus = 0, rc = device_cus(cus);
   if (rc != LIFEAPI_OK) return rc;
@@ -51,8 +50,7 @@ int lifeapi_stable_pass_batch_dev(uint64_t *d_planes, uint8_t *d_flags, size_t n
   if (n == 0) return LIFEAPI_OK;
   if (!d_planes || !d_flags || !aligned8(d_planes) || pass < 0 || pass > 5)
     return fail(LIFEAPI_E_INVALID, "bad argument to lifeapi_stable_pass_batch_dev%s");
-  const uintptr_t a = (uintptr_t)d_planes, b = (uintptr_t)d_flags;
-  if (b < a + n * 10 * 512 && a < b + n) return fail(LIFEAPI_E_INVALID, "flags overlap planes%s");
+  if (ranges_overlap(d_planes, n * 10 * 512, d_flags, n)) return fail(LIFEAPI_E_INVALID, "flags overlap planes%s");
   int cus = 0, rc = device_cus(cus);
   if (rc != LIFEAPI_OK) return rc;
   using Fn = void (*)(uint64_t *, uint8_t *, uint64_t, uint32_t, uint32_t);
@@ -135,8 +133,7 @@ int lifeapi_stable_vulnerable_batch_dev(const uint64_t *d_planes, uint64_t *d_ou
   if (n == 0) return LIFEAPI_OK;
   if (!d_planes || !d_out || !aligned8(d_planes) || !aligned8(d_out))
     return fail(LIFEAPI_E_INVALID, "bad pointer to lifeapi_stable_vulnerable_batch_dev%s");
-  const uintptr_t a = (uintptr_t)d_planes, b = (uintptr_t)d_out;
-  if (b < a + n * 10 * 512 && a < b + n * 512) return fail(LIFEAPI_E_INVALID, "out overlaps planes%s");
+  if (ranges_overlap(d_planes, n * 10 * 512, d_out, n * 512)) return fail(LIFEAPI_E_INVALID, "out overlaps planes%s");
   int cus = 0, rc = device_cus(cus);
   if (rc != LIFEAPI_OK) return rc;
   // as the passes: one wave per LifeStable, at most 4 blocks resident per
@@ -208,8 +205,7 @@ int lifeapi_refined_step_batch_dev(const uint64_t *d_in, uint64_t *d_out, size_t
   if (n == 0) return LIFEAPI_OK;
   if (!d_in || !d_out || !aligned8(d_in) || !aligned8(d_out))
     return fail(LIFEAPI_E_INVALID, "bad pointer to lifeapi_refined_step_batch_dev%s");
-  const uintptr_t a = (uintptr_t)d_in, b = (uintptr_t)d_out;
-  if (a < b + n * 3 * 512 && b < a + n * 11 * 512)
+  if (ranges_overlap(d_in, n * 11 * 512, d_out, n * 3 * 512))
     return fail(LIFEAPI_E_INVALID, "refined step input and output overlap%s");
   // the measured best with the 192-op SOP network (profiles/r01/tune_c5.jsonl):
   // prefetch the next universe, one-shot grid, no occupancy bound -> 6.3 TB/s

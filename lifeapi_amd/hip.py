@@ -107,12 +107,18 @@ def _stream(stream) -> int:
     return stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
 
 
-def _universes(t: torch.Tensor, name: str = "states") -> int:
+def _planes(t: torch.Tensor, k: int, name: str) -> int:
+    """n of a device tensor holding n universes of k 64-word planes each."""
     if not t.is_cuda:
         raise ValueError(f"{name} must be a device tensor")
-    if t.dtype not in (torch.int64, torch.uint64) or not t.is_contiguous() or t.numel() % N:
-        raise ValueError(f"{name} must be a contiguous int64 tensor of shape (n, 64)")
-    return t.numel() // N
+    if t.dtype not in (torch.int64, torch.uint64) or not t.is_contiguous() or t.numel() % (k * N):
+        shape = "(n, 64)" if k == 1 else f"(n, {k}*64)"
+        raise ValueError(f"{name} must be a contiguous int64 tensor of shape {shape}")
+    return t.numel() // (k * N)
+
+
+def _universes(t: torch.Tensor, name: str = "states") -> int:
+    return _planes(t, 1, name)
 
 
 def empty_universes(n: int, device=None) -> torch.Tensor:
@@ -260,10 +266,7 @@ def loaded_hip_runtimes() -> list[str]:
 def refined_step(planes: torch.Tensor, out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
     """Config-5 ternary step: (n, 11*64) int64 planes -> (n, 3*64) planes
     (see lifeapi_refined_step_batch_dev)."""
-    if not planes.is_cuda or planes.dtype not in (torch.int64, torch.uint64) or \
-            not planes.is_contiguous() or planes.numel() % (11 * N):
-        raise ValueError("planes must be a contiguous int64 device tensor of shape (n, 11*64)")
-    n = planes.numel() // (11 * N)
+    n = _planes(planes, 11, "planes")
     if out is None:
         out = torch.empty((n, 3 * N), dtype=torch.int64, device=planes.device)
     _check(lib.lifeapi_refined_step_batch_dev(planes.data_ptr(), out.data_ptr(), n, _stream(stream)))
@@ -273,10 +276,7 @@ def refined_step(planes: torch.Tensor, out: torch.Tensor | None = None, stream=N
 def weld_step(welds: torch.Tensor, generations: int = 1, stream=None) -> torch.Tensor:
     """LifeWeld::Step()^generations in place on (n, 4*64) {state, frozen2,
     frozen1, frozen0} planes (LifeWeld.hpp:169-186)."""
-    if not welds.is_cuda or welds.dtype not in (torch.int64, torch.uint64) or \
-            not welds.is_contiguous() or welds.numel() % (4 * N):
-        raise ValueError("welds must be a contiguous int64 device tensor of shape (n, 4*64)")
-    _check(lib.lifeapi_weld_step_batch_dev(welds.data_ptr(), welds.numel() // (4 * N), generations,
+    _check(lib.lifeapi_weld_step_batch_dev(welds.data_ptr(), _planes(welds, 4, "welds"), generations,
                                            _stream(stream)))
     return welds
 
@@ -289,10 +289,7 @@ def stable_pass(planes: torch.Tensor, which: str | int, max_iters: int = 0,
     """LifeStable pass in place on (n, 10*64) planes; returns uint8 flags
     (bit0 consistent, bit1 changed, bit2 stopped by max_iters)."""
     w = STABLE_PASSES.index(which) if isinstance(which, str) else int(which)
-    if not planes.is_cuda or planes.dtype not in (torch.int64, torch.uint64) or \
-            not planes.is_contiguous() or planes.numel() % (10 * N):
-        raise ValueError("planes must be a contiguous int64 device tensor of shape (n, 10*64)")
-    n = planes.numel() // (10 * N)
+    n = _planes(planes, 10, "planes")
     flags = torch.empty(n, dtype=torch.uint8, device=planes.device)
     _check(lib.lifeapi_stable_pass_batch_dev(planes.data_ptr(), flags.data_ptr(), n, w, max_iters,
                                              _stream(stream)))
@@ -301,10 +298,7 @@ def stable_pass(planes: torch.Tensor, which: str | int, max_iters: int = 0,
 
 def stable_vulnerable(planes: torch.Tensor, stream=None) -> torch.Tensor:
     """LifeStable::Vulnerable() (LifeStable.hpp:366-412) of (n, 10*64) planes -> (n, 64)."""
-    if not planes.is_cuda or planes.dtype not in (torch.int64, torch.uint64) or \
-            not planes.is_contiguous() or planes.numel() % (10 * N):
-        raise ValueError("planes must be a contiguous int64 device tensor of shape (n, 10*64)")
-    n = planes.numel() // (10 * N)
+    n = _planes(planes, 10, "planes")
     out = torch.empty((n, N), dtype=torch.int64, device=planes.device)
     _check(lib.lifeapi_stable_vulnerable_batch_dev(planes.data_ptr(), out.data_ptr(), n, _stream(stream)))
     return out

@@ -3,7 +3,9 @@ lifeapi_step_contains_batch (device = -1: contiguous shards, one host thread
 each, the arrays pinned once for all shards; host.hip over_devices).  A 1-GPU box has one device, so the shard count is
 forced with LIFEAPI_HOST_SHARDS (shard s on device s mod ndev): the threads,
 the shard arithmetic and the shared pins all run as they would over 8 GPUs.  Checked against the reference's own Step() (oracle/_ref)
-where built, else the C port."""
+where built, else the C port.  Also here: the Contains target, which the host
+calls stage with every chunk of every shard (host.hip host_chunked,
+HostIO::whole)."""
 import os
 
 import numpy as np
@@ -143,6 +145,114 @@ def test_sharded_host_forms(hip, shards, k):
         call("lifeapi_stable_vulnerable_batch", st0.ctypes.data, vul.ctypes.data, n, dev)
         return st, flags, vul
     host_twice(stable)
+
+
+def _block_and_ring():
+    blk, ring = np.zeros(64, np.uint64), np.zeros(64, np.uint64)
+    blk[20] = blk[21] = np.uint64(0b11 << 30)
+    for c in (19, 20, 21, 22):
+        ring[c] = np.uint64(0b1111 << 29)
+    return blk, ring & ~blk
+
+
+def _contains_host(hip, x, wanted, unwanted, device=0):
+    out = np.full(len(x), 7, np.uint8)
+    hip._check(hip.lib.lifeapi_contains_batch(x.ctypes.data, wanted.ctypes.data, unwanted.ctypes.data,
+                                              out.ctypes.data, len(x), device))
+    return out
+
+
+@pytest.fixture(scope="module")
+def three_chunks():
+    """Sparse soups with the block-and-ring target planted every tenth
+    universe, as test_gpu_parity.test_host_step_contains builds them, and the
+    oracle's Contains and 2-generation search loop.  512 + 256 staged bytes
+    per universe and 64 MiB chunks: 87,381 universes per chunk, so 180,001 is
+    three chunks on two lanes (the third reuses the first's buffer, target
+    slots included) and the last chunk is ragged."""
+    from oracle.oracle import Port, Ref
+    P, n = Port(), 180_001
+    blk, ring = _block_and_ring()
+    x = P.fill(n, seed=61) & P.fill(n, seed=62) & P.fill(n, seed=63)
+    x[::5] &= ~ring & ~blk
+    x[::10] |= blk
+    if Ref.available():
+        R = Ref()
+        hit = R.contains_batch(x, blk, ring)
+        first, fin = R.step_contains_batch(x, blk, ring, 2, nthreads=8)
+    else:
+        def contains(s):
+            return (((s ^ blk) & (blk | ring)) == 0).all(axis=1)
+        hit = contains(x).astype(np.uint8)
+        first, fin = np.zeros(n, np.uint32), x
+        for g in (1, 2):
+            fin = P.step_batch(fin, 1, nthreads=8)
+            first[(first == 0) & contains(fin)] = g
+    for want in (hit, first):  # the first and the third chunk both have hits to lose
+        assert want[:200].any() and want[-200:].any()
+    for a in (x, hit, first, fin):
+        a.flags.writeable = False
+    return x, blk, ring, hit, first, fin
+
+
+@pytest.mark.parametrize("device,k", [(0, None), (-1, 3)])
+def test_target_restaged_across_lane_reuse(hip, three_chunks, shards, device, k):
+    """the target is staged with every chunk (host.hip host_chunked): every
+    chunk of a three-chunk call, and every shard, tests against it"""
+    if k:
+        shards(k)
+    x, blk, ring, hit, first, fin = three_chunks
+    assert (_contains_host(hip, x, blk, ring, device) == hit).all()
+    assert (hip.step_contains_host(x, blk, ring, 2, device=device) == first).all()
+    y = x.copy()
+    assert (hip.step_contains_host(y, blk, ring, 2, final=y, device=device) == first).all()
+    assert (y == fin).all()
+
+
+def test_no_stale_target(hip):
+    """consecutive host Contains calls on the same states: each result follows
+    the target current at its call, whether the second target is another pair
+    of arrays or the first pair rewritten in place"""
+    from oracle.oracle import Port
+    P, n = Port(), 2001
+    x = P.fill(n, seed=71) & P.fill(n, seed=72)
+    blk, ring = _block_and_ring()
+    x[::10] = (x[::10] & ~ring) | blk
+    targets = [(blk, ring), (x[7] & x[8], ~(x[7] | x[8]) & ring)]
+    want = [np.array([P.contains(s, w, u) for s in x], np.uint8) for w, u in targets]
+    assert all(0 < e.sum() < n for e in want) and (want[0] != want[1]).any()
+    for e, (w, u) in zip(want, targets):
+        assert (_contains_host(hip, x, w, u) == e).all()
+    w, u = np.empty(64, np.uint64), np.empty(64, np.uint64)
+    for k in (0, 1, 0):
+        w[:], u[:] = targets[k]
+        assert (_contains_host(hip, x, w, u) == want[k]).all()
+
+
+def _at_4_mod_8(a):
+    """a copy of uint64 array `a` at an address that is 4 mod 8"""
+    buf = np.zeros(a.nbytes + 8, np.uint8)
+    at = (4 - buf.ctypes.data) % 8
+    b = buf[at:at + a.nbytes].view(np.uint64).reshape(a.shape)
+    b[...] = a
+    assert b.ctypes.data % 8 == 4
+    return b
+
+
+def test_unaligned_target_arrays(hip):
+    """wanted / unwanted at an address that is 4 mod 8 are accepted (they are
+    copied to 8-byte-aligned device memory); states there are rejected"""
+    from oracle.oracle import Port
+    P, n = Port(), 5
+    x = P.fill(n, seed=81) & P.fill(n, seed=82)
+    blk, ring = _block_and_ring()
+    x[1::2] = (x[1::2] & ~ring) | blk
+    want = np.array([P.contains(s, blk, ring) for s in x], np.uint8)
+    assert want.any() and not want.all()
+    assert (_contains_host(hip, x, _at_4_mod_8(blk), _at_4_mod_8(ring)) == want).all()
+    with pytest.raises(hip.LifeApiError) as e:
+        _contains_host(hip, _at_4_mod_8(x), blk, ring)
+    assert e.value.code == -1  # LIFEAPI_E_INVALID
 
 
 def test_bad_device_index(hip):

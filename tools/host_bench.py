@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Host-pointer path (lifeapi_step_batch on pageable numpy arrays, the C++
-facade's StepBatch) against the PCIe copy rates torch gets for the same
-bytes (pageable and pinned, each direction).  One JSON line per case."""
+facade's StepBatch; the host Contains and Step+Contains calls) against the
+PCIe copy rates torch gets for the same bytes (pageable and pinned, each
+direction).  One JSON line per case.  LIFEAPI_HIP_LIB=<another build of the
+library> measures that build instead (an A/B runs the two alternately)."""
 import json
 import os
 import sys
@@ -33,24 +35,40 @@ def main():
     nbytes = x.nbytes
     dev = torch.empty(n * 64, dtype=torch.int64, device="cuda")
     out = np.zeros_like(x)  # touched: no page faults inside the timed calls
+    reps = 3 if n > (1 << 16) else 101  # a small n measures the call's latency: more repeats
+    # the host search calls, whose target is staged with each chunk: Contains,
+    # and Step + Contains over 2 generations without final states.
+    w, u = np.zeros(64, np.uint64), np.zeros(64, np.uint64)
+    w[20] = w[21] = np.uint64(0b11 << 30)
+    u[19] = u[22] = np.uint64(0b1111 << 29)
+    hit = np.zeros(n, np.uint8)
+
+    def contains_host():
+        hip._check(hip.lib.lifeapi_contains_batch(x.ctypes.data, w.ctypes.data, u.ctypes.data,
+                                                  hit.ctypes.data, n, 0))
+    for case, gens, fn in (("contains_host", 0, contains_host),
+                           ("step_contains_host", 2, lambda: hip.step_contains_host(x, w, u, 2))):
+        t = wall(fn, reps)
+        print(json.dumps({"case": case, "universes": n, "gens": gens, "s": t, "universes_per_s": n / t}),
+              flush=True)
     for gens in (1, 1024):
         if gens == 1024 and n > (1 << 16):
             continue
         for case, kw in (("step_host", {"out": out}), ("step_host_inplace", {"out": x}),
                          ("step_host_fresh_out", {})):
-            t = wall(lambda: hip.step_host(x, generations=gens, **kw))
+            t = wall(lambda: hip.step_host(x, generations=gens, **kw), reps)
             print(json.dumps({"case": case, "universes": n, "gens": gens, "s": t,
                               "universe_gen_per_s": n * gens / t,
                               "GBps_round_trip": 2 * nbytes / t / 1e9}), flush=True)
         def pin_each_call():  # registration inside the timed call, as a library-side pin would
             with hip.host_pinned(x, out):
                 hip.step_host(x, generations=gens, out=out)
-        t = wall(pin_each_call)
+        t = wall(pin_each_call, reps)
         print(json.dumps({"case": "step_host_register_per_call", "universes": n, "gens": gens, "s": t,
                           "universe_gen_per_s": n * gens / t}), flush=True)
         with hip.host_pinned(x, out):  # page-locked once (lifeapi_host_register)
             for case, o in (("step_host_pinned", out), ("step_host_pinned_inplace", x)):
-                t = wall(lambda: hip.step_host(x, generations=gens, out=o))
+                t = wall(lambda: hip.step_host(x, generations=gens, out=o), reps)
                 print(json.dumps({"case": case, "universes": n, "gens": gens, "s": t,
                                   "universe_gen_per_s": n * gens / t,
                                   "GBps_round_trip": 2 * nbytes / t / 1e9}), flush=True)
