@@ -1,6 +1,8 @@
 """CPU: the generated pair-layout loop (tools/gen_pair_asm.py ->
-tools/tune/pair_asm.inc) is up to date and -- run on numpy lanes -- computes
-the oracle's Step() for 8 universes (2 groups x 4, two columns per lane)."""
+tools/tune/pair_asm.inc) is up to date and -- its text executed as emitted on
+tools/gfx950_asm.py's machine (labels, branches, waits, LDS at the byte
+addresses the kernel passes) -- computes the oracle's Step() for 8 universes
+(2 groups x 4, two columns per lane)."""
 import os
 import sys
 
@@ -45,3 +47,10 @@ def test_simulated_loop_is_step(port, variant):
         got = g.simulate(*_pack(x), gens, variant)
         want = _pack(port.step_batch(x, gens))
         assert (got[0] == want[0]).all() and (got[1] == want[1]).all(), (variant, gens)
+
+
+@pytest.mark.parametrize("variant", g.VARIANTS)
+def test_zero_generations_change_nothing(port, variant):
+    a, b = _pack(port.fill(8, seed=91))
+    got = g.simulate(a, b, 0, variant)
+    assert (got[0] == a).all() and (got[1] == b).all()

@@ -1,7 +1,8 @@
 """CPU: the generated rule-11 assembly loop (tools/gen_split_asm.py ->
-lifeapi_amd/csrc/split_asm.inc) is up to date, keeps its bank rules, and -- run
-on numpy lanes -- computes gen_split's network (the oracle's Step() on the
-8-way split layout)."""
+lifeapi_amd/csrc/split_asm.inc) is up to date, keeps its bank rules, and -- its
+text executed as emitted on tools/gfx950_asm.py's machine (labels, branches,
+waits, LDS at the byte addresses the kernel passes) -- computes gen_split's
+network (the oracle's Step() on the 8-way split layout)."""
 import os
 import sys
 
@@ -11,6 +12,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import gen_split_asm as g  # noqa: E402
+from gfx950_asm import Machine  # noqa: E402
 
 
 def test_inc_is_generated():
@@ -154,31 +156,29 @@ def test_simulated_batched_contains(port, h, lay):
                   port.fill(1, seed=950 + h)[0]])
     xr, wr, mr = _rot_rows(x, y0), _rot_rows(wanted, y0), _rot_rows(wanted | unwanted, y0)
     W, M = _to_split(np.stack([wr] * 4)), _to_split(np.stack([mr] * 4))
-    with g.layout(lay):
-        for gens in (0, 1, 2, 3, 7, 8, 9, 15, 16, 21):
-            exp, s = [0] * 4, x.copy()
-            for k in range(1, gens + 1):
-                s = port.step_batch(s, 1)
-                for u in range(4):
-                    if not exp[u] and (((s[u] ^ wanted) & (wanted | unwanted)) == 0).all():
-                        exp[u] = k
-            got, hits = g.simulate_batch(_to_split(xr), W, M, gens, g.LOW_H if lay == "low" else h)
-            assert hits == exp, (h, gens, hits, exp)
-            assert (got == _to_split(_rot_rows(s, y0))).all()
-        assert len({e for e in exp[:3] if e}) >= 2, exp  # hits at two or more distinct generations
+    for gens in (0, 1, 2, 3, 7, 8, 9, 15, 16, 21):
+        exp, s = [0] * 4, x.copy()
+        for k in range(1, gens + 1):
+            s = port.step_batch(s, 1)
+            for u in range(4):
+                if not exp[u] and (((s[u] ^ wanted) & (wanted | unwanted)) == 0).all():
+                    exp[u] = k
+        got, hits = g.simulate_batch(_to_split(xr), W, M, gens, g.LOW_H if lay == "low" else h, layout=lay)
+        assert hits == exp, (h, gens, hits, exp)
+        assert (got == _to_split(_rot_rows(s, y0))).all()
+    assert len({e for e in exp[:3] if e}) >= 2, exp  # hits at two or more distinct generations
 
 
 def test_batched_dpp_chain_reaches_lane_63():
     """the six in-place DPP ORs leave the OR of all 64 lanes in lane 63, for
-    single-lane words at every lane (the simulator's DPP model: row_shr
+    single-lane words at every lane (the machine's DPP model: row_shr
     within rows of 16 lanes, row_bcast 15 / 31 into the masked rows)"""
     a = g.ACC_HI
     for lane in range(64):
-        v = np.zeros((g.N_VGPR_C, 64), np.uint32)
-        v[a, lane] = 1 << (lane % 32)
-        for line in g.batch_chain():
-            g._dpp(v, line)
-        assert v[a, 63] == 1 << (lane % 32), lane
+        m = Machine(g.N_VGPR_C, 0)
+        m.v[a, lane] = 1 << (lane % 32)
+        m.run(g.batch_chain())
+        assert m.v[a, 63] == 1 << (lane % 32), lane
 
 
 @pytest.mark.parametrize("rows", [0x1111111111111111, 0x8000400020001001, (1 << 64) - 1])
@@ -207,3 +207,23 @@ def test_simulated_batched_contains_any_target(port, rows):
         assert hits == exp, (hex(rows), gens, hits, exp)
         assert (got == _to_split(s)).all()
     assert exp[0] == 11 and exp[1] == 8 and exp[2] == 3, exp
+
+
+def test_zero_generations_change_nothing(port):
+    """every loop at 0 generations (the guard branch over the whole text):
+    the state is unchanged and no universe is hit"""
+    r, r2 = _to_split(port.fill(4, seed=77)), _to_split(port.fill(4, seed=78))
+    w, m = _to_split(port.fill(4, seed=80)), _to_split(port.fill(4, seed=81))
+    for v in g.VARIANTS:
+        assert (g.simulate(r, 0, variant=v) == r).all(), v
+    ga, gb = g.simulate(r, 0, two=r2)
+    assert (ga == r).all() and (gb == r2).all()
+    forms = [dict(lean=False), dict(lean=True)]
+    forms += [dict(lean=True, h=h, late=late) for h in range(1, 9) for late in (False, True)]
+    forms += [dict(lean=True, h=g.LOW_H, layout="low")]
+    for kw in forms:
+        got, hits = g.simulate_contains(r, w, m, 0, **kw)
+        assert (got == r).all() and hits == [0] * 4, kw
+    for lay, h in [("high", h) for h in range(1, 9)] + [("low", g.LOW_H)]:
+        got, hits = g.simulate_batch(r, w, m, 0, h, layout=lay)
+        assert (got == r).all() and hits == [0] * 4, (lay, h)

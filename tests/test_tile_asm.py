@@ -1,7 +1,8 @@
 """The generated tile-layout generation loop (tools/tune/tile_asm.inc,
 tools/gen_tile_asm.py) on CPU: the committed file is what the generator
 emits, no VALU reads two sources from one VGPR bank, and executing the
-assembly text on 64 simulated lanes steps 16 universes exactly as the oracle
+assembly text on the 64 lanes of tools/gfx950_asm.py's machine (labels,
+branches, waits, byte-addressed LDS) steps 16 universes exactly as the oracle
 does (the register layout is Split<8>'s: register j, bit 4k + u = universe u,
 row 8k + j; lane i of group g owns columns 4(i mod 16) .. +3 of universes
 4g .. 4g+3)."""

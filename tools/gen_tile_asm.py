@@ -16,8 +16,10 @@ instruction reads distinct banks by construction:
   tail    s0 a+1, s1 a+2, s2 a+1, s3 a+3, t1 a+3, t2 a    (a = bank of the centre)
 
 The network is RULE 3's (device.hpp kLe1 .. kT3) exactly as gen_tile computes it
-(split_layout.hpp).  `simulate()` executes the generated text on numpy lanes;
-tests/test_tile_asm.py checks it against the oracle on CPU.
+(split_layout.hpp).  The emitting helpers and the interpreter of the emitted
+text are tools/gfx950_asm.py's; tests/test_tile_asm.py runs the committed
+file's lines on its machine (labels, branches, waits, byte-addressed LDS)
+against the oracle on CPU and checks the constraint lists against them.
 
 Usage: python tools/gen_tile_asm.py [--check]   (--check: fail if the .inc differs)
 """
@@ -26,14 +28,13 @@ from __future__ import annotations
 import os
 import sys
 
-import numpy as np
+from gfx950_asm import (EVEN, LE1, MAJ, NAE, T1, T2, T3, XOR3, AsmFn, Machine, Pool, bank_conflicts, op, render_fn,
+                        sreg, vreg)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OUT = os.path.join(ROOT, "tools", "tune", "tile_asm.inc")
 
 S, C, P = 8, 4, 4            # row split, columns per lane, universes per group
-XOR3, MAJ, LE1, NAE, EVEN = 0x96, 0xE8, 0x17, 0x7E, 0x69
-T1, T2, T3 = 0x34, 0x58, 0x28
 PLANE = 1024                 # bytes of one 16-B-per-lane LDS plane
 
 
@@ -57,19 +58,6 @@ A_SELF, A_PREV, A_NEXT = 120, 121, 122
 N_VGPR = 123
 
 
-class Alloc:
-    """Temps by bank; a register is free again after the last read of its value."""
-
-    def __init__(self):
-        self.free = {b: [r for r in TEMPS if r % 4 == b] for b in range(4)}
-
-    def get(self, bank):
-        return self.free[bank % 4].pop(0)
-
-    def put(self, r):
-        self.free[r % 4].append(r)
-
-
 def hcol(c, cols, slot):
     """h0/h1 of column c (register maps `cols`, LV/RV at the ends) into `slot`"""
     base = H_SLOTS[slot]
@@ -83,7 +71,7 @@ def hcol(c, cols, slot):
     return ops
 
 
-def out_col(c, a_reg, dst, slot, al: Alloc):
+def out_col(c, a_reg, dst, slot, al: Pool):
     """the rule tail of column c from H slot `slot`: centre a_reg(j), result
     to dst(j) (dst may be a_reg: a is dead after t2).  Temps from `al`."""
     base = H_SLOTS[slot]
@@ -138,7 +126,7 @@ def out_col(c, a_reg, dst, slot, al: Alloc):
     return ops
 
 
-def out_col_skew(c, a_reg, dst, slot, al: Alloc):
+def out_col_skew(c, a_reg, dst, slot, al: Pool):
     """out_col with the rows software-pipelined: step k issues row k's four
     s-functions interleaved with t1 of row k-1, t2 of row k-2 and T3 of row
     k-3, so every dependent pair is about six instructions apart"""
@@ -217,21 +205,20 @@ def fetch():
             ("ds_read", RV(0), A_NEXT, 0 * PLANE), ("ds_read", RV(4), A_NEXT, 1 * PLANE)]
 
 
-def generation(cols, e0, e3, lds=True):
+def generation(cols, e0, e3):
     """One generation, software-pipelined around the exchange: on entry LV/RV
     hold this generation's edges (reads in flight).  The edge columns are
     computed first into the spare sets e0 / e3 and published, the next
     generation's edges are fetched, and the interior columns (about 150 VALU)
     cover the LDS round trip.  Returns (ops, new column maps)."""
-    al = Alloc()
+    al = Pool(TEMPS)   # a register is free again after the last read of its value
     ops = [("waitcnt",)]
     ops += hcol(0, cols, 0)                     # A: LV, c0, c1
     ops += TAIL(0, cols[0], e0, 0, al)          # new column 0 -> e0 (c0 kept for hcol 1)
     ops += hcol(C - 1, cols, 1)                 # B: c2, c3, RV
     ops += TAIL(C - 1, cols[C - 1], e3, 1, al)
-    if lds:
-        ops += publish(e0, e3)
-        ops += fetch()                          # next generation's edges
+    ops += publish(e0, e3)
+    ops += fetch()                              # next generation's edges
     ops += hcol(1, cols, 0)                     # A: c0 (old), c1, c2
     ops += hcol(2, cols, 1)                     # B: c1, c2, c3 (old)
     ops += TAIL(1, cols[1], cols[1], 0, al)     # in place
@@ -240,41 +227,33 @@ def generation(cols, e0, e3, lds=True):
     return ops, [e0, cols[1], cols[2], e3]
 
 
-def check_banks(ops):
-    for op in ops:
-        if op[0] == "bitop3":
-            srcs = set(op[2])
-            assert len({r % 4 for r in srcs}) == len(srcs), f"bank conflict in {op}"
-
-
-def render(op):
-    k = op[0]
+def render(o):
+    k = o[0]
     if k == "bitop3":
-        d, (a, b, c), t = op[1], op[2], op[3]
-        return f"v_bitop3_b32 v{d}, v{a}, v{b}, v{c} bitop3:0x{t:x}"
+        return op(o[1], *o[2], o[3])
     if k == "alignbit":
-        d, (a, b), s = op[1], op[2], op[3]
+        d, (a, b), s = o[1], o[2], o[3]
         return f"v_alignbit_b32 v{d}, v{a}, v{b}, {s}"
     if k == "ds_write":
-        return f"ds_write_b128 v{op[1]}, v[{op[2]}:{op[2] + 3}] offset:{op[3]}"
+        return f"ds_write_b128 v{o[1]}, v[{o[2]}:{o[2] + 3}] offset:{o[3]}"
     if k == "ds_read":
-        return f"ds_read_b128 v[{op[1]}:{op[1] + 3}], v{op[2]} offset:{op[3]}"
+        return f"ds_read_b128 v[{o[1]}:{o[1] + 3}], v{o[2]} offset:{o[3]}"
     if k == "waitcnt":
         return "s_waitcnt lgkmcnt(0)"
     if k == "mov":
-        return f"v_mov_b32 v{op[1]}, v{op[2]}"
+        return f"v_mov_b32 v{o[1]}, v{o[2]}"
     if k == "raw":
-        return op[1]
-    raise ValueError(op)
+        return o[1]
+    raise ValueError(o)
 
 
-def program(lds=True):
+def program():
     """the whole asm block: prologue (publish, fetch), a loop of generation
     pairs (the spare edge sets swap back after two), an odd generation, and
     the final copy of the edge columns home"""
     cols0 = [col_map(c, 8 * c) for c in range(C)]
-    gA, cols1 = generation(cols0, E0, E3, lds)
-    gB, cols2 = generation(cols1, cols0[0], cols0[C - 1], lds)
+    gA, cols1 = generation(cols0, E0, E3)
+    gB, cols2 = generation(cols1, cols0[0], cols0[C - 1])
     assert [f(j) for f in cols2 for j in range(S)] == [f(j) for f in cols0 for j in range(S)]
     prog = [("raw", "s_cmp_eq_u32 %[g], 0"), ("raw", "s_cbranch_scc1 4f")]
     prog += publish(cols0[0], cols0[C - 1]) + fetch()
@@ -290,48 +269,42 @@ def program(lds=True):
     return prog, gA
 
 
-def emit(lds=True, name="tile_gens_asm") -> str:
-    prog, gen = program(lds)
+def check_banks(ops):
+    bad = bank_conflicts([render(o) for o in ops])[1]
+    assert not bad, f"bank conflict in {bad}"
+
+
+def function():
+    prog = program()[0]
     check_banks(prog)
-    body = [render(op) for op in prog]
-    n_valu = sum(op[0] in ("bitop3", "alignbit") for op in gen)
-    state = [f'"+{{v{ST(c, j)}}}"(r[{c}][{j}])' for c in range(C) for j in range(S)]
-    clob = [r for r in range(32, N_VGPR) if r not in (A_SELF, A_PREV, A_NEXT)]
-    lines = [
-        "// tile_asm.inc -- GENERATED by tools/gen_tile_asm.py; do not edit.",
-        "// The generation loop of the tile layout (RULE 8, 8-way row split, 4 columns",
-        "// per lane, LDS edge exchange) with every VALU source in a distinct VGPR",
-        "// bank, software-pipelined around the exchange.",
-        f"// {n_valu} VALU + 8 LDS per generation for 16 universes; {N_VGPR} VGPRs pinned.",
-        "#pragma once",
-        "",
-        "namespace lifeapi_impl {",
-        "",
-        "// r: the tile's state (gen_tile's r[c][j]); a_self / a_prev / a_next: LDS",
-        "// byte addresses of this lane's / lane i-1's / lane i+1's 16-B slot in the",
-        "// wave's four 1-KiB planes (lanes of the lane's 16-lane group, mod 16)",
-        f"__device__ __forceinline__ void {name}(uint32_t (&r)[4][8], uint32_t gens, uint32_t a_self,",
-        "                                              uint32_t a_prev, uint32_t a_next) {",
-        "  uint32_t pairs;",
-        "  asm volatile(",
-    ]
-    lines += [f'      "{b}\\n"' for b in body]
-    lines += [
-        "      : " + ",\n        ".join(state) + ",",
-        '        [p] "=&s"(pairs)',
-        f'      : [g] "s"(gens), "{{v{A_SELF}}}"(a_self), "{{v{A_PREV}}}"(a_prev), "{{v{A_NEXT}}}"(a_next)',
-        "      : " + ", ".join(f'"v{r}"' for r in clob) + ', "scc", "memory");',
-        "}",
-        "",
-        "}  // namespace lifeapi_impl",
-        "",
-    ]
-    return "\n".join(lines)
+    lines = [render(o) for o in prog]
+    return AsmFn(
+        name="tile_gens_asm",
+        sig="(uint32_t (&r)[4][8], uint32_t gens, uint32_t a_self,\n" + " " * 46 + "uint32_t a_prev, uint32_t a_next)",
+        comment="// r: the tile's state (gen_tile's r[c][j]); a_self / a_prev / a_next: LDS\n"
+                "// byte addresses of this lane's / lane i-1's / lane i+1's 16-B slot in the\n"
+                "// wave's four 1-KiB planes (lanes of the lane's 16-lane group, mod 16)",
+        decls=("uint32_t pairs;",), lines=lines,
+        outs=[[vreg(ST(c, j), f"r[{c}][{j}]", "+")] for c in range(C) for j in range(S)] +
+             [[sreg("p", "pairs", "=&s")]],
+        ins=[[sreg("g", "gens", "s"), vreg(A_SELF, "a_self"), vreg(A_PREV, "a_prev"), vreg(A_NEXT, "a_next")]],
+        clobbers=[r for r in range(32, N_VGPR) if r not in (A_SELF, A_PREV, A_NEXT)])
 
 
-# ---------------------------------------------------------------------------
-# simulator of the generated text (64 lanes, numpy) for the CPU tests
-# ---------------------------------------------------------------------------
+def emit() -> str:
+    n_valu = sum(o[0] in ("bitop3", "alignbit") for o in program()[1])
+    return f"""// tile_asm.inc -- GENERATED by tools/gen_tile_asm.py; do not edit.
+// The generation loop of the tile layout (RULE 8, 8-way row split, 4 columns
+// per lane, LDS edge exchange) with every VALU source in a distinct VGPR
+// bank, software-pipelined around the exchange.
+// {n_valu} VALU + 8 LDS per generation for 16 universes; {N_VGPR} VGPRs pinned.
+#pragma once
+
+namespace lifeapi_impl {{
+{render_fn(function())}
+}}  // namespace lifeapi_impl
+"""
+
 
 def parse_program(text: str):
     """the instruction lines of the asm block, in order"""
@@ -343,70 +316,14 @@ def parse_program(text: str):
     return out
 
 
-def _v(tok):
-    return int(tok.strip().lstrip("v").split(":")[0].lstrip("["))
-
-
-def simulate(prog, regs: np.ndarray, lds: np.ndarray, gens: int):
-    """execute the asm block on 64 lanes: regs uint32 [N_VGPR, 64]; lds uint8"""
-    sreg = {"%[g]": gens, "%[p]": 0}
-    scc = 0
-    labels = {ins[:-1]: i for i, ins in enumerate(prog) if ins.endswith(":")}
-    pc = 0
-    while pc < len(prog):
-        ins = prog[pc]
-        pc += 1
-        if ins.endswith(":"):
-            continue
-        op, _, rest = ins.partition(" ")
-        args = [a.strip() for a in rest.split(",")]
-        if op == "v_bitop3_b32":
-            d, a, b = _v(args[0]), _v(args[1]), _v(args[2])
-            c_tok, t_tok = args[3].split()
-            t = int(t_tok.split(":")[1], 16)
-            A, B, Cc = regs[a].copy(), regs[b].copy(), regs[_v(c_tok)].copy()
-            res = np.zeros(64, np.uint32)
-            for idx in range(8):  # minterm idx = (src0, src1, src2) bits
-                if (t >> idx) & 1:
-                    res |= ((A if idx & 4 else ~A) & (B if idx & 2 else ~B) & (Cc if idx & 1 else ~Cc))
-            regs[d] = res
-        elif op == "v_alignbit_b32":
-            d, a, b, sh = _v(args[0]), _v(args[1]), _v(args[2]), int(args[3])
-            wide = (regs[a].astype(np.uint64) << 32) | regs[b].astype(np.uint64)
-            regs[d] = ((wide >> np.uint64(sh)) & 0xFFFFFFFF).astype(np.uint32)
-        elif op == "v_mov_b32":
-            regs[_v(args[0])] = regs[_v(args[1])]
-        elif op == "ds_write_b128":
-            addr, base = _v(args[0]), _v(args[1].split()[0])
-            off = int(args[1].split("offset:")[1])
-            for lane in range(64):
-                at = int(regs[addr][lane]) + off
-                lds[at:at + 16] = np.ascontiguousarray(regs[base:base + 4, lane]).view(np.uint8)
-        elif op == "ds_read_b128":
-            base = _v(args[0])
-            addr, off = _v(args[1].split()[0]), int(args[1].split("offset:")[1])
-            vals = np.zeros((4, 64), np.uint32)
-            for lane in range(64):
-                at = int(regs[addr][lane]) + off
-                vals[:, lane] = lds[at:at + 16].view(np.uint32)
-            regs[base:base + 4] = vals
-        elif op == "s_waitcnt":
-            pass
-        elif op == "s_cmp_eq_u32":
-            scc = int(sreg[args[0]] == int(args[1]))
-        elif op == "s_cmp_lg_u32":
-            scc = int(sreg[args[0]] != int(args[1]))
-        elif op == "s_bitcmp1_b32":
-            scc = (sreg[args[0]] >> int(args[1])) & 1
-        elif op == "s_lshr_b32":
-            sreg[args[0]] = sreg[args[1]] >> int(args[2])
-        elif op == "s_sub_u32":
-            sreg[args[0]] = sreg[args[1]] - int(args[2])
-        elif op in ("s_cbranch_scc0", "s_cbranch_scc1"):
-            if scc == (op == "s_cbranch_scc1"):
-                pc = labels[args[0][:-1]]
-        else:
-            raise ValueError(ins)
+def simulate(prog, regs, lds, gens: int):
+    """execute the asm block's lines on 64 lanes: regs uint32 [N_VGPR, 64]
+    (the state and the LDS addresses in, the state out); lds uint8 (its size
+    in, its bytes out)"""
+    m = Machine(N_VGPR, len(lds), g=gens)
+    m.v[:] = regs
+    m.run(prog)
+    regs[:], lds[:] = m.v, m.lds
 
 
 def main():
