@@ -16,6 +16,7 @@ import pytest
 import torch
 
 from test_gpu_parity import to_dev, to_host
+from test_launch_paths import source_constant
 
 pytestmark = pytest.mark.gpu
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", "tune"))
@@ -140,11 +141,13 @@ def test_interleaved_batches_equal_reference(hip, stepper, n):
         assert (to_host(a) == want_a[k]).all() and (to_host(b) == want_b[k]).all(), k
 
 
-def test_interleaved_filter_and_step(hip, stepper):
-    """the search filter with final states (order-keyed up to 2M universes)
-    reading what the step wrote, and the step reading the filter's output"""
+@pytest.mark.parametrize("n", [20001, source_constant("kOrderMinUniverses") + 5],
+                         ids=["below_order_min", "order_keyed"])
+def test_interleaved_filter_and_step(hip, stepper, n):
+    """the search filter with final states (order-keyed from kOrderMinUniverses
+    up to 2M universes) reading what the step wrote, and the step reading the
+    filter's output; below the threshold every launch runs forward"""
     from oracle.oracle import Port
-    n = 20001
     x = Port().fill(n, seed=77)
     w, u = np.zeros(64, np.uint64), np.zeros(64, np.uint64)
     w[3] = np.uint64(6)
