@@ -27,15 +27,15 @@
 // are shared with the iterated search loop's k_step_contains_split
 // (contains_kernels.hpp).  This file holds the kernels that run them:
 // k_cone_adapt (shipped: the chunk of universes per wave chosen from the
-// window) and k_cone (fixed shapes, the tuning build's A/Bs), with their
-// launchers.
+// window) and k_cone (fixed shapes, the tuning build's A/Bs).  Their
+// launchers are host code: cone_launch.hpp (k_cone_adapt, with the shipped
+// shape's measurements) and tools/tune/tune_cone.hip (k_cone).
 #pragma once
 
 #include <type_traits>
 
 #include "cone_passes.hpp"
 #include "cone_split.hpp"
-#include "host.hpp"
 
 namespace lifeapi_impl {
 // internal linkage: every library that includes this header gets its own
@@ -238,30 +238,6 @@ __global__ __launch_bounds__(kBlock) void k_cone_adapt(const uint64_t *in, const
   }
 }
 
-// The shipped shape (round 4's last): k_cone_adapt, register sets 8 at a
-// time, at most 16 blocks per CU, for Contains and the 1-2 generation filter.
-// Same process, 1M universes, back to back (tools/cone_ab.py,
-// profiles/r04/r04x/cone_ab.jsonl), against k_cone with 64 universes per wave
-// on a one-shot grid (shipped before): filter 0.0223 / 0.0226 ms on the
-// 4-column target, 0.0436 / 0.0471 on 14 columns, 0.0658 / 0.0696 on 30, the
-// whole board 0.0884 / 0.0898; Contains 0.0199 / 0.0213, 0.0409 / 0.0411,
-// 0.0616 / 0.0626, 0.0790 / 0.0803.  Caps of 4 / 8 / 32 and no cap: slower
-// on some target each (32: +7 % on the 4-column filter; none: +40 %).
-// k_cone's fixed shapes, before: 64 per wave best for P <= 8 (0.0270 against
-// 0.0288 ms with 32 per wave, each launch after a scrub,
-// profiles/r04/r04g/cone_grid_ab.jsonl), 16 per wave best for 14-30 columns.
-constexpr int kConeSets = 8;
-constexpr int kConeAdaptBlocksPerCU = 16;
-// (Round 5 routed the filter without final states by the generation count,
-// the batch size and the last launch report: k_cone_adapt alone up to 4
-// generations (6 for batches of at most 256K), the row-window passes up to
-// 15, the split pair beyond; its constants and measurements are in the git
-// history and DESIGN.md 3.2.)
-// Round 6: the merged split kernel (step.hip, 3+ generations without final
-// states) on a grid of at most this many blocks per CU looping over the
-// batch (1M universes: 16 and 32 within 1-3 % of each other on every
-// target, 8 up to 9 % slower on the one-row whole board; profiles/r06/ab/)
-constexpr int kFilterIterBlocksPerCU = 16;
 // (kConeRowsWindowGens, kConeWholeWinGens: cone_window.hpp)
 // The iterated search loop (gens > 2, no final states) steps the light cone
 // while it spans at most this many columns (P <= 32 lanes per universe: at
@@ -272,65 +248,6 @@ constexpr int kFilterIterBlocksPerCU = 16;
 // one wave per SIMD).
 constexpr uint32_t kConeIterColumns = 32;
 static_assert(kConeIterColumns <= 32, "kContainsLo's cone passes take P <= 32");
-// The split kernels (step.hip, with or without final states) run on grids of
-// at most 32 blocks per CU looping over the batch: one of the two always
-// idles, and the working one is faster capped from 256K universes on.
-constexpr int kSplitIterBlocksPerCU = 32;
-// The tuning build's separate-launch form of the same (k_cone before the
-// pair): 8 universes per wave.
-constexpr int kConeIterUniverses = 8;
-
-// Launches k_cone on a one-shot grid.
-template <int UPW, int RMAX, bool FIRST, typename OutT, bool PIPE = false>
-int launch_cone(const uint64_t *d_in, const uint64_t *d_wanted, const uint64_t *d_unwanted, OutT *d_out, size_t n,
-                uint32_t gens, int cus, hipStream_t stream, int blocks_per_cu = 0, uint32_t kmax = kWave) {
-  const dim3 grid(grid_for((n + UPW - 1) / UPW, cus, blocks_per_cu));
-  bool a16 = false;
-  if constexpr (!FIRST) a16 = aligned16(d_in);
-  if constexpr (!FIRST) {
-    if (a16) {
-      hipLaunchKernelGGL((k_cone<UPW, RMAX, FIRST, OutT, true, PIPE>), grid, dim3(kBlock), 0, stream, d_in, d_wanted,
-                         d_unwanted, d_out, (uint64_t)n, gens, kmax);
-      return launched("k_cone launch");
-    }
-  }
-  hipLaunchKernelGGL((k_cone<UPW, RMAX, FIRST, OutT, false, PIPE>), grid, dim3(kBlock), 0, stream, d_in, d_wanted,
-                     d_unwanted, d_out, (uint64_t)n, gens, kmax);
-  return launched("k_cone launch");
-}
-
-// Launches k_cone_adapt on ceil(n / 16) waves, at most blocks_per_cu blocks
-// per CU (0: no cap).  DMA: a whole-board window takes cone_wave_full_dma
-// when the batch is 16-byte aligned, on a grid of at most dma_blocks_per_cu
-// blocks per CU (0: uncapped; blocks_per_cu then caps the waves of a
-// windowed target).
-template <int RMAX, bool FIRST, typename OutT, bool DMA = false, bool ROWS = true, bool WIN = false, bool EARLY = true>
-int launch_cone_adapt(const uint64_t *d_in, const uint64_t *d_wanted, const uint64_t *d_unwanted, OutT *d_out,
-                      size_t n, uint32_t gens, int cus, hipStream_t stream, int blocks_per_cu,
-                      uint32_t kmax = kWave, int dma_blocks_per_cu = 0) {
-  const dim3 grid(grid_for((n + 15) / 16, cus, blocks_per_cu));
-  if constexpr (DMA) {
-    if (aligned16(d_in)) {
-      const uint32_t cap_waves = blocks_per_cu > 0 ? (uint32_t)(cus * blocks_per_cu * kWavesPerBlock) : 0u;
-      hipLaunchKernelGGL((k_cone_adapt<RMAX, FIRST, OutT, true, true, ROWS, WIN, EARLY>),
-                         dim3(grid_for((n + 15) / 16, cus, dma_blocks_per_cu)), dim3(kBlock), 0, stream, d_in,
-                         d_wanted, d_unwanted, d_out, (uint64_t)n, gens, kmax, cap_waves);
-      return launched("k_cone_adapt launch");
-    }
-  }
-  bool a16 = false;
-  if constexpr (!FIRST) a16 = aligned16(d_in);
-  if (a16) {
-    if constexpr (!FIRST) {
-      hipLaunchKernelGGL((k_cone_adapt<RMAX, FIRST, OutT, true, false, ROWS, WIN>), grid, dim3(kBlock), 0, stream, d_in,
-                         d_wanted, d_unwanted, d_out, (uint64_t)n, gens, kmax, 0u);
-      return launched("k_cone_adapt launch");
-    }
-  }
-  hipLaunchKernelGGL((k_cone_adapt<RMAX, FIRST, OutT, false, false, ROWS, WIN>), grid, dim3(kBlock), 0, stream, d_in,
-                     d_wanted, d_unwanted, d_out, (uint64_t)n, gens, kmax, 0u);
-  return launched("k_cone_adapt launch");
-}
 
 }  // namespace
 }  // namespace lifeapi_impl

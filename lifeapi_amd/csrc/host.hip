@@ -12,7 +12,7 @@
 #include <tuple>
 #include <vector>
 
-#include "host.hpp"
+#include "launch.hpp"
 
 namespace lifeapi_impl {
 
@@ -138,7 +138,7 @@ static int occupancy_lds_uncached(const void *kernel, int blocks_per_cu, unsigne
   return LIFEAPI_OK;
 }
 
-// ---- launch order keyed on the batch (host.hpp launch_reverse) ----
+// ---- launch order keyed on the batch (launch.hpp launch_reverse) ----
 namespace {
 constexpr int kOrderDevices = 64, kOrderSlots = 8;
 struct OrderSlot {

@@ -1,14 +1,19 @@
 // reduce.hip -- per-universe reductions and synthetic input: GetPop
 // (LifeAPI.hpp:290-298), Contains(LifeTarget) (LifeTarget.hpp:44-51), the
 // build-defined hash, and the seeded RandomState()-style fill.
+#include "cone_launch.hpp"
 #include "device.hpp"
-#include "host.hpp"
+#include "launch.hpp"
 #include "reduce_kernels.hpp"
-#include "cone_kernels.hpp"
 
 using namespace lifeapi_impl;
 
 namespace {
+
+// k_pop<kRedU> (reduce_kernels.hpp): a grid of at most 32 blocks per CU
+// looping over the batch (full grids and plain loads were 6-20 % slower,
+// profiles/r01/red_ab.jsonl).
+constexpr int kRedBlocksPerCU = 32;
 
 // build-defined universe hash: mix(sum_x mix(s[x] + (x+1)*G)).  The
 // per-word mix is heavy (four 64-bit multiplies), so the cross-lane sum must
@@ -80,31 +85,23 @@ int lifeapi_pop_batch_dev(const uint64_t *d_states, uint32_t *d_pop, size_t n, v
   if (n == 0) return LIFEAPI_OK;
   if (!d_states || !d_pop || !aligned8(d_states) || ((uintptr_t)d_pop & 3u))
     return fail(LIFEAPI_E_INVALID, "bad pointer to lifeapi_pop_batch_dev%s");
-  int cus = 0, rc = device_cus(cus);
-  if (rc != LIFEAPI_OK) return rc;
   // 16-byte loads (two universes per wave-instruction), 8 universes per
   // wave, one-shot grid: 0.0820 ms on 1M against 0.0918 for the 8-byte
   // k_pop<4> on the 32-blocks-per-CU grid, same process (tools/ab/rows_ab.py,
   // profiles/r03/rows_ab.jsonl); batches that are only 8-byte aligned keep
   // the 8-byte kernel
   if (aligned16(d_states))
-    hipLaunchKernelGGL(k_pop16<8>, dim3(grid_for((n + 7) / 8, cus, 0)), dim3(kBlock), 0, (hipStream_t)stream,
-                       d_states, d_pop, (uint64_t)n);
-  else
-    hipLaunchKernelGGL(k_pop<kRedU>, dim3(grid_for((n + kRedU - 1) / kRedU, cus, kRedBlocksPerCU)), dim3(kBlock),
-                       0, (hipStream_t)stream, d_states, d_pop, (uint64_t)n);
-  return launched("k_pop launch");
+    return launch(k_pop16<8>, "k_pop launch", Grid{(n + 7) / 8}, stream, kWritesNoBatch, d_states, d_pop, n);
+  return launch(k_pop<kRedU>, "k_pop launch", Grid{(n + kRedU - 1) / kRedU, kRedBlocksPerCU}, stream, kWritesNoBatch,
+                d_states, d_pop, n);
 }
 
 int lifeapi_hash_batch_dev(const uint64_t *d_states, uint64_t *d_hash, size_t n, void *stream) {
   if (n == 0) return LIFEAPI_OK;
   if (!d_states || !d_hash || !aligned8(d_states) || !aligned8(d_hash))
     return fail(LIFEAPI_E_INVALID, "bad pointer to lifeapi_hash_batch_dev%s");
-  int cus = 0, rc = device_cus(cus);
-  if (rc != LIFEAPI_OK) return rc;
-  hipLaunchKernelGGL(k_hash, dim3(grid_for((n + kHashU - 1) / kHashU, cus, 0)), dim3(kBlock), 0,
-                     (hipStream_t)stream, d_states, d_hash, (uint64_t)n);
-  return launched("k_hash launch");
+  return launch(k_hash, "k_hash launch", Grid{(n + kHashU - 1) / kHashU}, stream, kWritesNoBatch, d_states, d_hash,
+                n);
 }
 
 int lifeapi_contains_batch_dev(const uint64_t *d_states, const uint64_t *d_wanted,
@@ -114,11 +111,9 @@ int lifeapi_contains_batch_dev(const uint64_t *d_states, const uint64_t *d_wante
   if (!d_states || !d_wanted || !d_unwanted || !d_out || !aligned8(d_states) ||
       !aligned8(d_wanted) || !aligned8(d_unwanted))
     return fail(LIFEAPI_E_INVALID, "bad pointer to lifeapi_contains_batch_dev%s");
-  int cus = 0, rc = device_cus(cus);
-  if (rc != LIFEAPI_OK) return rc;
   // only the columns holding the target's care cells (cone_kernels.hpp)
-  return launch_cone_adapt<kConeSets, false>(d_states, d_wanted, d_unwanted, d_out, n, 0u, cus,
-                                             (hipStream_t)stream, kConeAdaptBlocksPerCU);
+  return launch_cone_adapt<kConeSets, false>(d_states, d_wanted, d_unwanted, d_out, n, 0u, 0, (hipStream_t)stream,
+                                             kConeAdaptBlocksPerCU);
 }
 
 int lifeapi_fill_random_dev(uint64_t *d_out, size_t n, uint64_t seed, uint64_t first_universe,
@@ -126,19 +121,12 @@ int lifeapi_fill_random_dev(uint64_t *d_out, size_t n, uint64_t seed, uint64_t f
   if (n == 0) return LIFEAPI_OK;
   if (!d_out || !aligned8(d_out) || (mode != 0 && mode != 1))
     return fail(LIFEAPI_E_INVALID, "bad argument to lifeapi_fill_random_dev%s");
-  int cus = 0, rc = device_cus(cus);
-  if (rc != LIFEAPI_OK) return rc;
   const uint64_t words = (uint64_t)n * kWave;
-  note_forward_write(d_out, words * 8);
   // 16-byte stores (two words per lane): 0.0836 ms on 1M against 0.0862 for
   // 8-byte ones (tools/ab/rows_ab.py, profiles/r03/rows_ab.jsonl)
-  if (aligned16(d_out))
-    hipLaunchKernelGGL(k_fill16, dim3(grid_for(words / (2 * kWave), cus, 0)), dim3(kBlock), 0,
-                       (hipStream_t)stream, d_out, words, seed, first_universe * kWave, mode);
-  else
-    hipLaunchKernelGGL(k_fill, dim3(grid_for(words / kWave, cus, 0)), dim3(kBlock), 0,
-                       (hipStream_t)stream, d_out, words, seed, first_universe * kWave, mode);
-  return launched("k_fill launch");
+  const bool wide = aligned16(d_out);
+  return launch(wide ? k_fill16 : k_fill, "k_fill launch", Grid{words / (wide ? 2 * kWave : kWave)}, stream,
+                Written{d_out, words * 8}, d_out, words, seed, first_universe * kWave, mode);
 }
 
 }  // extern "C"

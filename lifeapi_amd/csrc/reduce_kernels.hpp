@@ -15,11 +15,9 @@ namespace {
 // sum over the wave by DPP (wave_sum_*_dpp), not through ds_bpermute.
 constexpr int kRedU = 4;  // (templates below take U; the launches pick it)
 
-// The states are read once: nontemporal loads, and a grid of at most 32
-// blocks per CU looping over the batch (full grids and plain loads were 6-20 %
-// slower, profiles/r01/red_ab.jsonl).
-constexpr int kRedBlocksPerCU = 32;
-
+// The states are read once: nontemporal loads (and a capped grid looping over
+// the batch, reduce.hip kRedBlocksPerCU; full grids and plain loads were
+// 6-20 % slower, profiles/r01/red_ab.jsonl).
 __device__ __forceinline__ uint64_t ld_state(const uint64_t *p) { return __builtin_nontemporal_load(p); }
 
 // GetPop (LifeAPI.hpp:290-298): two universes' popcounts per 32-bit reduction

@@ -4,7 +4,7 @@
 #include <vector>
 
 #include "device.hpp"
-#include "host.hpp"
+#include "launch.hpp"
 
 using namespace lifeapi_impl;
 
@@ -221,6 +221,7 @@ struct DevBufs {
   }
 };
 constexpr size_t kRleChunk = size_t(1) << 18;  // patterns per device pass
+constexpr int kRleBlocksPerCU = 8;  // the RLE kernels' grids: one wave per pattern, looping over the batch
 
 }  // namespace
 
@@ -230,11 +231,8 @@ int lifeapi_rle_lengths_batch_dev(const uint64_t *d_states, uint32_t *d_len, siz
   if (n == 0) return LIFEAPI_OK;
   if (!d_states || !d_len || !aligned8(d_states) || ((uintptr_t)d_len & 3u))
     return fail(LIFEAPI_E_INVALID, "bad pointer to lifeapi_rle_lengths_batch_dev%s");
-  int cus = 0, rc = device_cus(cus);
-  if (rc != LIFEAPI_OK) return rc;
-  hipLaunchKernelGGL(k_rle<false>, dim3(grid_for(n, cus, 8)), dim3(kBlock), 0, (hipStream_t)stream,
-                     d_states, d_len, nullptr, nullptr, (uint64_t)n);
-  return launched("k_rle launch");
+  return launch(k_rle<false>, "k_rle launch", Grid{n, kRleBlocksPerCU}, stream, kWritesNoBatch, d_states, d_len,
+                nullptr, nullptr, n);
 }
 
 int lifeapi_rle_write_batch_dev(const uint64_t *d_states, const uint64_t *d_offsets, char *d_text,
@@ -242,11 +240,8 @@ int lifeapi_rle_write_batch_dev(const uint64_t *d_states, const uint64_t *d_offs
   if (n == 0) return LIFEAPI_OK;
   if (!d_states || !d_offsets || !d_text || !aligned8(d_states) || !aligned8(d_offsets))
     return fail(LIFEAPI_E_INVALID, "bad pointer to lifeapi_rle_write_batch_dev%s");
-  int cus = 0, rc = device_cus(cus);
-  if (rc != LIFEAPI_OK) return rc;
-  hipLaunchKernelGGL(k_rle<true>, dim3(grid_for(n, cus, 8)), dim3(kBlock), 0, (hipStream_t)stream,
-                     d_states, nullptr, d_offsets, d_text, (uint64_t)n);
-  return launched("k_rle launch");
+  return launch(k_rle<true>, "k_rle launch", Grid{n, kRleBlocksPerCU}, stream, kWritesNoBatch, d_states, nullptr,
+                d_offsets, d_text, n);
 }
 
 int lifeapi_parse_rle_batch_dev(const char *d_text, const uint64_t *d_offsets, size_t n, uint64_t *d_out,
@@ -254,12 +249,8 @@ int lifeapi_parse_rle_batch_dev(const char *d_text, const uint64_t *d_offsets, s
   if (n == 0) return LIFEAPI_OK;
   if (!d_text || !d_offsets || !d_out || !d_status || !aligned8(d_offsets) || !aligned8(d_out))
     return fail(LIFEAPI_E_INVALID, "bad pointer to lifeapi_parse_rle_batch_dev%s");
-  int cus = 0, rc = device_cus(cus);
-  if (rc != LIFEAPI_OK) return rc;
-  note_forward_write(d_out, (uint64_t)n * 512);
-  hipLaunchKernelGGL(k_parse_rle, dim3(grid_for(n, cus, 8)), dim3(kBlock), 0, (hipStream_t)stream,
-                     d_text, d_offsets, d_out, d_status, (uint64_t)n);
-  return launched("k_parse_rle launch");
+  return launch(k_parse_rle, "k_parse_rle launch", Grid{n, kRleBlocksPerCU}, stream,
+                Written{d_out, (uint64_t)n * 512}, d_text, d_offsets, d_out, d_status, n);
 }
 
 int lifeapi_rle_batch(const uint64_t *states, size_t n, char *text, size_t text_cap, uint64_t *offsets,

@@ -7,8 +7,9 @@
 // tools/tune/tune_step.hip, and are not part of this library.
 #include <algorithm>
 
-#include "cone_kernels.hpp"
+#include "cone_launch.hpp"
 #include "contains_kernels.hpp"
+#include "launch.hpp"
 #include "step_kernels.hpp"
 
 using namespace lifeapi_impl;
@@ -39,7 +40,7 @@ using StepFn = void (*)(const uint64_t *, uint64_t *, uint64_t, uint32_t, uint64
 // stores wants fewer waves resident.  The sweep on the new body (universes per
 // wave {4, 8} x resident blocks per CU {all 8, 7, 6} x plain tail x order, or
 // x XCD chunks above 4M) moved these, each by more than 3 x the spread:
-// * resident blocks per CU (unused dynamic LDS, host.hip occupancy_lds): 7
+// * resident blocks per CU (unused dynamic LDS, launch.hpp Grid): 7
 //   at 1M universes (0.1461 against 0.1475 ms uncapped), 6 from 2M on (2M
 //   0.3131 against 0.3216 uncapped and 0.3167 with 7; 4M 0.6571 against
 //   0.6810 / 0.6722; 8M 1.296 against 1.318 / 1.303; 16M 2.664 against 3.011
@@ -58,7 +59,7 @@ using StepFn = void (*)(const uint64_t *, uint64_t *, uint64_t, uint32_t, uint64
 // Launch order and store policy (tools/ab/order_ab.py, profiles/r02/order_*.jsonl,
 // same process, ping-pong as the bench): a launch whose input batch an
 // earlier launch wrote takes the groups in the reverse of that launch's order
-// (host.hpp launch_reverse, keyed on the batch), so it starts on what was
+// (launch.hpp launch_order, keyed on the batch), so it starts on what was
 // written last; the groups that store the last min(256 MiB, half
 // the batch) of a launch use plain stores, which leave that part in the 256 MB
 // memory-side Infinity Cache, and the rest nontemporal ones, which do not
@@ -112,6 +113,115 @@ StepLaunch shipped_step(uint32_t gens, uint64_t n) {
           "k_step_split<8-way split, 4 universes/wave, 6-LUT tail, assembly loop>", 0u};
 }
 
+// ---- lifeapi_step_contains_batch_dev: its four forms ----
+
+// The merged split kernel (below, 3+ generations without final states) on a
+// grid of at most this many blocks per CU looping over the batch (round 6; 1M
+// universes: 16 and 32 within 1-3 % of each other on every target, 8 up to
+// 9 % slower on the one-row whole board; profiles/r06/ab/)
+constexpr int kFilterIterBlocksPerCU = 16;
+// The split pair (below, final states at 3+ generations) runs on grids of at
+// most 32 blocks per CU looping over the batch: one of the two always idles,
+// and the working one is faster capped from 256K universes on.
+constexpr int kSplitIterBlocksPerCU = 32;
+
+using SplitFn = void (*)(const uint64_t *, uint64_t *, const uint64_t *, const uint64_t *, uint32_t *, uint64_t,
+                         uint32_t, uint32_t);
+
+// First hits only at 1-2 generations, the search filter proper: the
+// target's light cone, or the whole board, in the natural layout
+// (cone_kernels.hpp k_cone_adapt, DMA form): a whole-board target takes
+// the universes through LDS (cone_passes.hpp cone_wave_full_dma / cone_wave_rows_dma, 8
+// per pass by global_load_lds, the next pass fetched while this one
+// steps), every other window its cone (cone_wave); every wave decides,
+// on a grid of at most kConeAdaptBlocksPerCU blocks per CU looping over
+// the batch.  Round 6: no launch report -- round 5 chose the grid per
+// target pointers from the last call's report, which a loop that rewrites
+// its target buffers read stale (+13 % per call, tools/report_loop_probe.py,
+// profiles/r06/).  1M universes, median of 5 x 10 back to back
+// (tools/filter_iter_probe.py, profiles/r06/): the one-row whole board
+// 0.083 / 0.086 ms at 1 / 2 generations against 0.082 / 0.081 on the
+// reported uncapped grid, the full-height and random whole boards 5-9 %
+// faster, the block + ring unchanged (0.023 / 0.026).
+int filter_cone(const uint64_t *d_in, const uint64_t *d_wanted, const uint64_t *d_unwanted, uint32_t *d_first_gen,
+                size_t n, uint32_t generations, void *stream) {
+  return launch_cone_adapt<kConeSets, true, uint32_t, true>(d_in, d_wanted, d_unwanted, d_first_gen, n, generations, 0,
+                                                            (hipStream_t)stream, kConeAdaptBlocksPerCU, kWave,
+                                                            kConeAdaptBlocksPerCU);
+}
+
+// First hits only at 3+ generations (round 6): one launch of the merged
+// split kernel (contains_kernels.hpp k_step_contains_split, kContainsAll),
+// whose waves take the pass their target calls for -- no report, so a
+// loop that rewrites its target buffers loses nothing:
+// * care rows that fit 32 with the light cone (cone_rows): on a whole
+//   board below kConeWholeWinGens generations the packed LDS-DMA pass
+//   (cone_wave_rows_dma), else the window split layout (cone_split.hpp)
+//   on the column window, on half the lanes once the cone's columns fit
+//   (a whole board's chunks fetched by LDS-DMA);
+// * else a cone of <= 32 columns: the natural layout on the cone
+//   (cone_wave);
+// * else the 8-way row split with the test fused (the loop its row
+//   window picks), the next group of universes fetched into LDS while
+//   this one steps.
+// 1M universes, median of 5 x 10 back to back (tools/filter_iter_probe.py,
+// profiles/r06/): block + ring at 3 / 5 / 8 / 13 generations 0.042 / 0.058
+// / 0.096 / 0.137 ms (round 5: 0.047 / 0.057 / 0.154 / 0.222;
+// profiles/r06/shrink_ab/), a full-height target 0.179 / 0.235 / 0.309 /
+// 0.435 (0.18 / 0.24 / 0.32 / 0.47 on the split pair).
+int filter_iterated(const uint64_t *d_in, const uint64_t *d_wanted, const uint64_t *d_unwanted,
+                    uint32_t *d_first_gen, size_t n, uint32_t generations, void *stream) {
+  const SplitFn fn = aligned16(d_in) ? k_step_contains_split<8, kContainsNet, kContainsAll, true, true>
+                                     : k_step_contains_split<8, kContainsNet, kContainsAll, false, true>;
+  return launch(fn, "k_step_contains_split launch", Grid{(n + 3) / 4, kFilterIterBlocksPerCU}, stream,
+                kWritesNoBatch, d_in, nullptr, d_wanted, d_unwanted, d_first_gen, n, generations, kConeIterColumns);
+}
+
+// Final states at 3+ generations, in the layout of the shipped step for
+// gens > 2: two kernels, one per register layout (a target window of <= 4
+// rows in 62 VGPRs, 8 waves per SIMD; the rest in 71, 7 waves): each wave
+// finds the window and only the matching kernel works (contains_kernels.hpp
+// kContainsLo / kContainsHi); every universe steps the whole board (no light
+// cone: the kernels' last argument is 0).  Both grids are capped (blocks per
+// CU, looping over the batch), so that the idle kernel's waves cost a few
+// microseconds instead of a wave launch per 4 universes
+// (tools/ab/search_iter_caps_ab.py): 1M universes x 8 / 64
+// generations 0.467 -> 0.394-0.398 / 1.78-1.80 -> 1.70 ms, 256K 0.112 ->
+// 0.101 ms; at config 3's 64K the cap does not bind (tools/ab/final_caps_ab.py,
+// profiles/r04/r04ar).
+int final_split_pair(const uint64_t *d_in, uint64_t *d_final, const uint64_t *d_wanted, const uint64_t *d_unwanted,
+                     uint32_t *d_first_gen, size_t n, uint32_t generations, void *stream) {
+  int cus = 0, rc = device_cus(cus);  // (once for both launches)
+  Written w{d_final, (uint64_t)n * 512};  // (recorded once for the pair)
+  for (const SplitFn fn : {SplitFn(k_step_contains_split<8, kContainsNet, kContainsLo>),
+                           SplitFn(k_step_contains_split<8, kContainsNet, kContainsHi>)}) {
+    if (rc != LIFEAPI_OK) return rc;
+    rc = launch(fn, "k_step_contains_split launch", Grid{(n + 3) / 4, kSplitIterBlocksPerCU, 0, cus}, stream, w, d_in,
+                d_final, d_wanted, d_unwanted, d_first_gen, n, generations, 0u);
+    w.recorded = true;
+  }
+  return rc;
+}
+
+// Final states at 1-2 generations: k_step_contains<8>, 8 universes per wave,
+// every block slot (tools/ab/filter_ab.py, profiles/r02/filter_ab.jsonl, 1M
+// universes x 1 generation, same process): 0.181 ms with final states
+// (5.96 TB/s on 1028 B per universe); 4 per wave 0.179, with fewer blocks
+// resident slower; one per wave 0.229.
+// The launch order and plain-stored tail of the step (above): a loop that
+// filters the states the last call left gets them partly from the Infinity
+// Cache (tools/ab/filter_order_ab.py).  Up to 2M universes: +3.4 % at 512K
+// and 1M, +2 % at 2M, none at 4M (profiles/r02/filter_order_ab.jsonl).
+int final_stream(const uint64_t *d_in, uint64_t *d_final, const uint64_t *d_wanted, const uint64_t *d_unwanted,
+                 uint32_t *d_first_gen, size_t n, uint32_t generations, void *stream) {
+  const uint64_t groups = (n + 7) / 8;
+  const bool keyed = n <= kFilterOrderUniverses && n >= kOrderMinUniverses;
+  const LaunchOrder o = launch_order(d_in, d_final, (uint64_t)n * 512, groups, 8 * 512, keyed,
+                                     keyed ? std::min<uint64_t>(kPlainBytes, n * 512 / 2) : 0);
+  return launch(k_step_contains<8>, "k_step_contains launch", Grid{groups}, stream, o.written, d_in, d_final,
+                d_wanted, d_unwanted, d_first_gen, n, generations | (o.reverse ? kReverse : 0u), o.plain_from);
+}
+
 }  // namespace
 
 extern "C" {
@@ -125,26 +235,13 @@ int lifeapi_step_batch_dev(const uint64_t *d_in, uint64_t *d_out, size_t n, uint
                            void *stream) {
   int rc = check_batch(d_in, d_out, n);
   if (rc != LIFEAPI_OK || n == 0) return rc;
-  int cus = 0;
-  rc = device_cus(cus);
-  if (rc != LIFEAPI_OK) return rc;
   const StepLaunch l = shipped_step(generations, n);
   const uint64_t waves = (n + l.universes_per_wave - 1) / l.universes_per_wave;
-  unsigned lds = 0;
-  if (l.resident_blocks) {
-    rc = occupancy_lds(reinterpret_cast<const void *>(l.fn), l.resident_blocks, lds);
-    if (rc != LIFEAPI_OK) return rc;
-  }
-  const uint64_t plain = (l.plain_bytes + l.universes_per_wave * 512 - 1) / (l.universes_per_wave * 512);
-  uint32_t order = 0;
-  if (l.alternate && n >= kOrderMinUniverses) order = launch_reverse(d_in, d_out, (uint64_t)n * 512) ? kReverse : 0u;
-  else note_forward_write(d_out, (uint64_t)n * 512);
-  // one-shot: k_step's waves take one group each (step_body ONESHOT)
-  const unsigned grid = grid_for(waves, cus, 0);
-  if ((uint64_t)grid * kWavesPerBlock < waves) return fail(LIFEAPI_E_INVALID, "batch too large for one grid%s");
-  hipLaunchKernelGGL(l.fn, dim3(grid), dim3(kBlock), lds, (hipStream_t)stream, d_in,
-                     d_out, (uint64_t)n, generations | order | l.flags, plain < waves ? waves - plain : (uint64_t)0);
-  return launched("k_step launch");
+  const LaunchOrder o = launch_order(d_in, d_out, (uint64_t)n * 512, waves, l.universes_per_wave * 512,
+                                     l.alternate && n >= kOrderMinUniverses, l.plain_bytes);
+  // one-shot, and k_step's waves take one group each (step_body ONESHOT)
+  return launch(l.fn, "k_step launch", Grid{waves, 0, l.resident_blocks, 0, true}, stream, o.written, d_in, d_out, n,
+                generations | (o.reverse ? kReverse : 0u) | l.flags, o.plain_from);
 }
 
 int lifeapi_step_contains_batch_dev(const uint64_t *d_in, uint64_t *d_final,
@@ -155,114 +252,15 @@ int lifeapi_step_contains_batch_dev(const uint64_t *d_in, uint64_t *d_final,
   if (!d_in || !d_wanted || !d_unwanted || !d_first_gen || !aligned8(d_in) ||
       !aligned8(d_wanted) || !aligned8(d_unwanted) || ((uintptr_t)d_first_gen & 3u))
     return fail(LIFEAPI_E_INVALID, "bad pointer to lifeapi_step_contains_batch_dev%s");
-  if (d_final) {
-    int rc = check_batch(d_in, d_final, n);
-    if (rc != LIFEAPI_OK) return rc;
-  }
-  int cus = 0, rc = device_cus(cus);
-  if (rc != LIFEAPI_OK) return rc;
-  if (!d_final && generations <= 2) {
-    // the search filter proper (first hits only) at 1-2 generations: the
-    // target's light cone, or the whole board, in the natural layout
-    // (cone_kernels.hpp k_cone_adapt, DMA form): a whole-board target takes
-    // the universes through LDS (cone_passes.hpp cone_wave_full_dma / cone_wave_rows_dma, 8
-    // per pass by global_load_lds, the next pass fetched while this one
-    // steps), every other window its cone (cone_wave); every wave decides,
-    // on a grid of at most kConeAdaptBlocksPerCU blocks per CU looping over
-    // the batch.  Round 6: no launch report -- round 5 chose the grid per
-    // target pointers from the last call's report, which a loop that rewrites
-    // its target buffers read stale (+13 % per call, tools/report_loop_probe.py,
-    // profiles/r06/).  1M universes, median of 5 x 10 back to back
-    // (tools/filter_iter_probe.py, profiles/r06/): the one-row whole board
-    // 0.083 / 0.086 ms at 1 / 2 generations against 0.082 / 0.081 on the
-    // reported uncapped grid, the full-height and random whole boards 5-9 %
-    // faster, the block + ring unchanged (0.023 / 0.026).
-    return launch_cone_adapt<kConeSets, true, uint32_t, true>(d_in, d_wanted, d_unwanted, d_first_gen, n,
-                                                              generations, cus, (hipStream_t)stream,
-                                                              kConeAdaptBlocksPerCU, kWave, kConeAdaptBlocksPerCU);
-  }
   if (!d_final) {
-    // 3+ generations, first hits only (round 6): one launch of the merged
-    // split kernel (contains_kernels.hpp k_step_contains_split, kContainsAll),
-    // whose waves take the pass their target calls for -- no report, so a
-    // loop that rewrites its target buffers loses nothing:
-    // * care rows that fit 32 with the light cone (cone_rows): on a whole
-    //   board below kConeWholeWinGens generations the packed LDS-DMA pass
-    //   (cone_wave_rows_dma), else the window split layout (cone_split.hpp)
-    //   on the column window, on half the lanes once the cone's columns fit
-    //   (a whole board's chunks fetched by LDS-DMA);
-    // * else a cone of <= 32 columns: the natural layout on the cone
-    //   (cone_wave);
-    // * else the 8-way row split with the test fused (the loop its row
-    //   window picks), the next group of universes fetched into LDS while
-    //   this one steps.
-    // 1M universes, median of 5 x 10 back to back (tools/filter_iter_probe.py,
-    // profiles/r06/): block + ring at 3 / 5 / 8 / 13 generations 0.042 / 0.058
-    // / 0.096 / 0.137 ms (round 5: 0.047 / 0.057 / 0.154 / 0.222;
-    // profiles/r06/shrink_ab/), a full-height target 0.179 / 0.235 / 0.309 /
-    // 0.435 (0.18 / 0.24 / 0.32 / 0.47 on the split pair).
-    using Fn = void (*)(const uint64_t *, uint64_t *, const uint64_t *, const uint64_t *, uint32_t *, uint64_t,
-                        uint32_t, uint32_t);
-    const Fn fn = aligned16(d_in) ? k_step_contains_split<8, kContainsNet, kContainsAll, true, true>
-                                  : k_step_contains_split<8, kContainsNet, kContainsAll, false, true>;
-    hipLaunchKernelGGL(fn, dim3(grid_for((n + 3) / 4, cus, kFilterIterBlocksPerCU)), dim3(kBlock), 0,
-                       (hipStream_t)stream, d_in, (uint64_t *)nullptr, d_wanted, d_unwanted, d_first_gen, (uint64_t)n,
-                       generations, kConeIterColumns);
-    return launched("k_step_contains_split launch");
+    if (generations <= 2) return filter_cone(d_in, d_wanted, d_unwanted, d_first_gen, n, generations, stream);
+    return filter_iterated(d_in, d_wanted, d_unwanted, d_first_gen, n, generations, stream);
   }
-  if (generations > 2) {  // the layout of the shipped step for gens > 2
-    // Without final states, a target whose light cone over `generations`
-    // spans at most kConeIterColumns columns is answered on that cone:
-    // kContainsLo's waves step only those columns in the natural layout
-    // (cone_wave) and kContainsHi's return.  Both grids are capped (blocks
-    // per CU, looping over the batch), so that the idle kernel's waves cost a
-    // few microseconds instead of a wave launch per 4 universes
-    // (tools/ab/search_iter_caps_ab.py).  With final states
-    // the capped grids help too: 1M universes x 8 / 64
-    // generations 0.467 -> 0.394-0.398 / 1.78-1.80 -> 1.70 ms, 256K 0.112 ->
-    // 0.101 ms; at config 3's 64K the cap does not bind (tools/ab/final_caps_ab.py,
-    // profiles/r04/r04ar).
-    const int split_cap = kSplitIterBlocksPerCU;
-    const uint32_t cone_max = 0;  // (final states: every universe steps the whole board)
-    // two kernels, one per register layout (a target window of <= 4 rows in
-    // 62 VGPRs, 8 waves per SIMD; the rest in 71, 7 waves): each wave finds
-    // the window and only the matching kernel works (contains_kernels.hpp
-    // kContainsLo / kContainsHi)
-    using Fn = void (*)(const uint64_t *, uint64_t *, const uint64_t *, const uint64_t *, uint32_t *, uint64_t,
-                        uint32_t, uint32_t);
-    const Fn fns[2] = {k_step_contains_split<8, kContainsNet, kContainsLo>,
-                       k_step_contains_split<8, kContainsNet, kContainsHi>};
-    const dim3 grid(grid_for((n + 3) / 4, cus, split_cap));
-    if (d_final) note_forward_write(d_final, (uint64_t)n * 512);
-    for (const Fn fn : fns) {
-      hipLaunchKernelGGL(fn, grid, dim3(kBlock), 0, (hipStream_t)stream, d_in, d_final, d_wanted, d_unwanted,
-                         d_first_gen, (uint64_t)n, generations, cone_max);
-      rc = launched("k_step_contains_split launch");
-      if (rc != LIFEAPI_OK) return rc;
-    }
-    return LIFEAPI_OK;
-  } else {
-    // 8 universes per wave, every block slot (tools/ab/filter_ab.py,
-    // profiles/r02/filter_ab.jsonl, 1M universes x 1 generation, same
-    // process): 0.087 ms = 6.25 TB/s on the 516 B per universe of the bare
-    // filter, 0.181 ms with final states (5.96 TB/s on 1028 B); 4 per wave
-    // 0.107 / 0.179, with fewer blocks resident slower; one per wave 0.229.
-    // With final states, the launch order and plain-stored tail of the step
-    // (above): a loop that filters the states the last call left gets them
-    // partly from the Infinity Cache (tools/ab/filter_order_ab.py).
-    const uint64_t groups = (n + 7) / 8;
-    // Up to 2M universes: +3.4 % at 512K and 1M, +2 % at 2M, none at 4M
-    // (profiles/r02/filter_order_ab.jsonl).
-    const bool order = d_final && n <= kFilterOrderUniverses && n >= kOrderMinUniverses;
-    const uint64_t plain = order ? (std::min<uint64_t>(kPlainBytes, n * 512 / 2) + 8 * 512 - 1) / (8 * 512) : 0;
-    uint32_t rev = 0;
-    if (order) rev = launch_reverse(d_in, d_final, (uint64_t)n * 512) ? kReverse : 0u;
-    else if (d_final) note_forward_write(d_final, (uint64_t)n * 512);
-    hipLaunchKernelGGL(k_step_contains<8>, dim3(grid_for(groups, cus, 0)), dim3(kBlock), 0, (hipStream_t)stream,
-                       d_in, d_final, d_wanted, d_unwanted, d_first_gen, (uint64_t)n, generations | rev,
-                       plain < groups ? groups - plain : (uint64_t)0);
-  }
-  return launched("k_step_contains launch");
+  const int rc = check_batch(d_in, d_final, n);
+  if (rc != LIFEAPI_OK) return rc;
+  if (generations > 2)
+    return final_split_pair(d_in, d_final, d_wanted, d_unwanted, d_first_gen, n, generations, stream);
+  return final_stream(d_in, d_final, d_wanted, d_unwanted, d_first_gen, n, generations, stream);
 }
 
 }  // extern "C"

@@ -8,7 +8,6 @@
 // alternatives.
 #pragma once
 
-#include "host.hpp"
 #include "life_gen.hpp"
 #include "split_layout.hpp"
 #include "split_asm.inc"

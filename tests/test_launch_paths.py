@@ -2,7 +2,7 @@
 second call on the same batch or a stream of the caller's own reaches.
 
 * A -- the later chunks of every capped grid (step.hip, reduce.hip,
-  cone_kernels.hpp): a wave of k_cone_adapt, k_pop<kRedU> or the merged split
+  cone_launch.hpp): a wave of k_cone_adapt, k_pop<kRedU> or the merged split
   kernel takes a second chunk only once the batch exceeds blocks per CU x CUs
   x 4 waves x universes per chunk, which no other test's batch does;
 * B -- the reversed launch order of k_weld, k_step_contains<8> and k_step

@@ -37,7 +37,7 @@ def stepper():
 def test_shipped_occupancy_caps_are_exact(tune):
     """the streaming k_step's cap (7 blocks, step.hip kStreamResidentBlocks)
     and the LifeStable kernels' (3 for the single passes and 4 for
-    StabiliseOptions and Vulnerable, stencils.hip kStablePassResident)"""
+    StabiliseOptions and Vulnerable, stencils.hip kStablePasses)"""
     assert tune.capped_occupancy(0, 7) == 7
     for which in range(1, 8):
         for want in (3, 4):
@@ -113,6 +113,67 @@ def test_every_device_writer_records_its_output(tune, hip):
     planes = torch.zeros((n // 8, 11 * 64), dtype=torch.int64, device="cuda")
     out = torch.empty((n // 8, 3 * 64), dtype=torch.int64, device="cuda")
     check(out.data_ptr(), (n // 8) * 1536, lambda: hip.refined_step(planes, out=out))
+
+
+def _zeros(words: int, offset8: bool = False) -> torch.Tensor:
+    """int64 zeros on the device, 16-byte aligned or (offset8) only 8-byte aligned"""
+    t = torch.zeros(words + 1, dtype=torch.int64, device="cuda")
+    t = t[1:] if offset8 else t[:-1]
+    assert t.data_ptr() % 16 == (8 if offset8 else 0)
+    return t
+
+
+WRITER_CASES = ["step_below_order_min", "final_1gen_below_order_min", "final_split_pair_3gen",
+                "interaction_counts", "interaction_counts_and_next", "stable_vulnerable",
+                "weld_1gen", "weld_12gen"]
+WRITER_CASES += [f"stable_{which}_{form}" for which in ("sync", "options", "signal", "step", "propagate", "stabilise")
+                 for form in ("aligned16", "aligned8")]
+
+
+@pytest.mark.parametrize("case", WRITER_CASES)
+def test_device_writer_records_its_output(tune, hip, case):
+    """test_every_device_writer_records_its_output's check for the other entry
+    points that write a batch, each of their kernels once (4096 universes'
+    worth of memory): the step below kOrderMinUniverses; the two forms of the
+    fused step with final states (k_step_contains<8> below the threshold, the
+    split pair); the interaction counts; every LifeStable pass on a 16-byte
+    aligned batch (k_stable_dma, but for Propagate) and on one that is only
+    8-byte aligned (k_stable); Vulnerable; the weld below 12 generations
+    (order-keyed: in place it reads the reversed entry, so it writes forward)
+    and from 12.  A launch states the batch it writes (launch.hpp Written);
+    one that stated none would leave the reversed entry in the book."""
+    n = 4096
+    src = _zeros(n * 16 * 64).data_ptr()       # a stand-in input address (the book never reads memory)
+    zp = src + 8 * n * 512
+    y, z, zero = _zeros(n * 64), _zeros(n * 64), _zeros(64)
+    st = _zeros((n // 8) * 640, offset8=case.endswith("aligned8"))
+    stream = hip._stream(None)
+    if case == "step_below_order_min":
+        assert n < source_constant("kOrderMinUniverses")
+        out, nbytes, write = z, n * 512, lambda: hip.step(y, out=z, generations=1)
+    elif case == "final_1gen_below_order_min":
+        out, nbytes, write = z, n * 512, lambda: hip.step_contains(y, zero, zero, 1, final=z)
+    elif case == "final_split_pair_3gen":
+        out, nbytes, write = z, n * 512, lambda: hip.step_contains(y, zero, zero, 3, final=z)
+    elif case.startswith("interaction_counts"):
+        with_next = int(case.endswith("and_next"))
+        out, nbytes = _zeros(n * 4 * 64), n * (3 + with_next) * 512
+        write = lambda: hip._check(hip.lib.lifeapi_interaction_counts_batch_dev(  # noqa: E731
+            y.data_ptr(), out.data_ptr(), n, with_next, stream))
+    elif case == "stable_vulnerable":
+        out, nbytes = z, (n // 8) * 512
+        write = lambda: hip._check(hip.lib.lifeapi_stable_vulnerable_batch_dev(  # noqa: E731
+            st.data_ptr(), z.data_ptr(), n // 8, stream))
+    elif case.startswith("stable_"):
+        out, nbytes, write = st, (n // 8) * 5120, lambda: hip.stable_pass(st, case.split("_")[1])
+    else:
+        out, nbytes = _zeros((n // 4) * 256), (n // 4) * 2048
+        write = lambda: hip.weld_step(out, int(case[5:-3]))  # noqa: E731
+    tune.order_note(src, nbytes)
+    assert tune.order_probe(src, out.data_ptr(), nbytes) is True     # recorded as written in reverse
+    write()
+    torch.cuda.synchronize()
+    assert tune.order_probe(out.data_ptr(), zp, nbytes) is True      # rewritten forward: the next reader reverses
 
 
 @pytest.mark.parametrize("n", [1, 4099, 300000])

@@ -3,7 +3,9 @@
 facade's StepBatch; the host Contains and Step+Contains calls) against the
 PCIe copy rates torch gets for the same bytes (pageable and pinned, each
 direction).  One JSON line per case.  LIFEAPI_HIP_LIB=<another build of the
-library> measures that build instead (an A/B runs the two alternately)."""
+library> measures that build instead (an A/B runs the two alternately).
+`host_bench.py enqueue` measures the host cost per *_dev call instead
+(enqueue, below)."""
 import json
 import os
 import sys
@@ -28,7 +30,46 @@ def wall(fn, reps=3):
     return sorted(ts)[len(ts) // 2]
 
 
+def enqueue(n=64, calls=20000):
+    """The host cost of one *_dev call: `calls` calls on a batch of n back to
+    back on the current stream, a host clock around the loop, one synchronise
+    after it and none inside.  At 64 universes the kernels take a few
+    microseconds, so the loop measures what the library does on the host to
+    enqueue a launch (through ctypes: the same for every build)."""
+    L, st = hip.lib, hip._stream(None)
+    zeros = lambda words: torch.zeros(words, dtype=torch.int64, device="cuda")  # noqa: E731
+    x, y, w, u = hip.fill_random(n, seed=5), zeros(n * 64), zeros(64), zeros(64)
+    first, pop, flags = (torch.zeros(n, dtype=torch.int32, device="cuda") for _ in range(3))
+    planes, welds = zeros(n * 640), zeros(n * 256)
+    p = lambda t: t.data_ptr()  # noqa: E731
+    contains = lambda final, gens: lambda: L.lifeapi_step_contains_batch_dev(  # noqa: E731
+        p(x), final, p(w), p(u), p(first), n, gens, st)
+    cases = [("step_1gen", lambda: L.lifeapi_step_batch_dev(p(x), p(y), n, 1, st)),
+             ("step_8gen", lambda: L.lifeapi_step_batch_dev(p(x), p(y), n, 8, st)),
+             ("filter_cone_2gen", contains(None, 2)), ("filter_iterated_8gen", contains(None, 8)),
+             ("final_split_pair_8gen", contains(p(y), 8)), ("final_stream_2gen", contains(p(y), 2)),
+             ("stable_pass_0", lambda: L.lifeapi_stable_pass_batch_dev(p(planes), p(flags), n, 0, 0, st)),
+             ("stable_pass_4", lambda: L.lifeapi_stable_pass_batch_dev(p(planes), p(flags), n, 4, 0, st)),
+             ("weld_1gen", lambda: L.lifeapi_weld_step_batch_dev(p(welds), n, 1, st)),
+             ("pop", lambda: L.lifeapi_pop_batch_dev(p(x), p(pop), n, st))]
+    for case, fn in cases:
+        hip._check(fn())
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        bad = 0
+        for _ in range(calls):
+            bad |= fn()
+        t = time.perf_counter() - t0
+        torch.cuda.synchronize()
+        t_done = time.perf_counter() - t0  # (with the queue drained: the larger of the host's and the GPU's time)
+        hip._check(bad)
+        print(json.dumps({"case": "enqueue_" + case, "universes": n, "calls": calls, "us_per_call": 1e6 * t / calls,
+                          "us_per_call_drained": 1e6 * t_done / calls}), flush=True)
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "enqueue":  # host_bench.py enqueue [universes [calls]]
+        return enqueue(*(int(a) for a in sys.argv[2:4]))
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 1 << 20
     rng = np.random.default_rng(5)
     x = rng.integers(0, 2**63, size=(n, 64), dtype=np.uint64)

@@ -2,12 +2,31 @@
 // filter (k_cone, lifeapi_amd/csrc/cone_kernels.hpp) for A/Bs.  Every shape
 // computes the same answers as the shipped one.
 #include "lifeapi_tune.h"
-#include "cone_kernels.hpp"
+#include "cone_launch.hpp"
 #include "contains_kernels.hpp"
 
 using namespace lifeapi_impl;
 
 namespace {
+
+// The separate-launch form of the iterated search loop's cone pass (k_cone
+// before the split pair, lifeapi_tune_search_iter): 8 universes per wave.
+constexpr int kConeIterUniverses = 8;
+
+// Launches k_cone on ceil(n / UPW) waves, at most blocks_per_cu blocks per CU
+// (0: one-shot); Contains (!FIRST) over a 16-byte aligned batch takes the A16
+// form.
+template <int UPW, int RMAX, bool FIRST, typename OutT, bool PIPE = false>
+int launch_cone(const uint64_t *d_in, const uint64_t *d_wanted, const uint64_t *d_unwanted, OutT *d_out, size_t n,
+                uint32_t gens, int cus, hipStream_t stream, int blocks_per_cu = 0, uint32_t kmax = kWave) {
+  void (*fn)(const uint64_t *, const uint64_t *, const uint64_t *, OutT *, uint64_t, uint32_t, uint32_t) =
+      k_cone<UPW, RMAX, FIRST, OutT, false, PIPE>;
+  if constexpr (!FIRST) {
+    if (aligned16(d_in)) fn = k_cone<UPW, RMAX, FIRST, OutT, true, PIPE>;
+  }
+  return launch(fn, "k_cone launch", Grid{(n + UPW - 1) / UPW, blocks_per_cu, 0, cus}, stream, kWritesNoBatch, d_in,
+                d_wanted, d_unwanted, d_out, n, gens, kmax);
+}
 
 template <bool FIRST, typename OutT>
 int cone_by_shape(const uint64_t *in, const uint64_t *w, const uint64_t *u, OutT *out, size_t n, uint32_t gens,

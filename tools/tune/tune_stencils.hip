@@ -4,7 +4,7 @@
 // other streaming stencils (stencil_kernels.hpp) with an occupancy cap
 // (tools/ab/stencil_occupancy_ab.py).
 #include "lifeapi_tune.h"
-#include "host.hpp"
+#include "launch.hpp"
 #include "stable_kernels.hpp"
 #include "stencil_kernels.hpp"
 #include "step_kernels.hpp"
@@ -270,7 +270,7 @@ int lifeapi_tune_capped_occupancy(int which, int want, int *got) {
   return e == hipSuccess ? LIFEAPI_OK : fail_hip(e, "hipOccupancyMaxActiveBlocksPerMultiprocessor");
 }
 
-/* the product's launch-order book (host.hpp launch_reverse): 1 = a launch
+/* the product's launch-order book (launch.hpp launch_reverse): 1 = a launch
  * reading d_in (bytes) and writing d_out on the current device would take
  * the reverse order; records d_out, as the product's launchers do        */
 int lifeapi_tune_order_probe(const void *d_in, const void *d_out, uint64_t bytes) {

@@ -10,6 +10,7 @@
 
 #include "lifeapi_tune.h"
 #include "contains_kernels.hpp"
+#include "host.hpp"
 #include "step_kernels.hpp"
 #include "step_r6.hpp"
 #include "split_asm_tune.inc"
