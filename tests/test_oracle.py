@@ -205,13 +205,6 @@ def test_generated_circuit_is_the_table(inc, ttfile):
         assert (got == tt).all()
 
 
-def _inclusive_count(plane: np.ndarray) -> np.ndarray:
-    """NeighbourCount (NeighbourCount.hpp:40-70) per cell of a (64, 64) bool
-    plane on the torus: the 3x3 block's population, centre included"""
-    p = plane.astype(np.int64)
-    return sum(np.roll(np.roll(p, dx, 0), dy, 1) for dx in (-1, 0, 1) for dy in (-1, 0, 1))
-
-
 def test_reachable_rows_cover_every_neighbourhood():
     """The care sets of the resynthesised LifeStable networks
     (tools/cgp_stable.py reachable_rows) contain every input row the passes
@@ -222,27 +215,15 @@ def test_reachable_rows_cover_every_neighbourhood():
     from cgp_stable import reachable_rows
     care = {k: set(reachable_rows(k).tolist()) for k in ("count", "signal", "vulnerable")}
     rng = np.random.default_rng(2024)
-
-    def rowint(cols):
-        return sum(c.astype(np.int64) << i for i, c in enumerate(cols))
-
-    def bits(v, hi):
-        return [(v >> k) & 1 for k in range(hi, -1, -1)]
+    from stable_rows import cell_rows
     seen = {k: set() for k in care}
     for dens_s, dens_u in [(0.1, 0.1), (0.5, 0.5), (0.9, 0.05), (0.05, 0.9), (0.3, 0.0), (0.0, 0.3), (0.7, 0.7)]:
         for _ in range(3):
             st = rng.random((64, 64)) < dens_s
             un = rng.random((64, 64)) < dens_u
             opt = [rng.random((64, 64)) < 0.5 for _ in range(8)]
-            off = ~un & ~st
-            on_c, off_c = _inclusive_count(st), _inclusive_count(off)
-            m_c, u_c = _inclusive_count(st | un), _inclusive_count(un)
-            r = rowint(bits(on_c % 8, 2) + bits(off_c, 3) + [st, off])
-            seen["count"] |= set(r.ravel().tolist())
-            r = rowint(opt + bits(on_c % 8, 2) + bits(m_c, 3) + [st, un])
-            seen["signal"] |= set(r.ravel().tolist())
-            r = rowint(opt + bits(on_c % 8, 2) + bits(u_c, 3))
-            seen["vulnerable"] |= set(r.ravel().tolist())
+            for k, r in cell_rows(st, un, opt).items():   # the passes' row formation (tests/stable_rows.py)
+                seen[k] |= set(r.ravel().tolist())
     for k in care:
         assert seen[k] <= care[k], k
         assert len(seen[k]) > len(care[k]) // 10  # the sample reaches a good part of the set

@@ -24,7 +24,10 @@ the reference's fragment computes on every input the kernels see.
 
 reachable_rows(NAME) is the care set; tests/test_oracle.py checks every
 committed network against the table on it, and the GPU parity tests run the
-kernels against the reference on arbitrary planes."""
+kernels against the reference on arbitrary planes.  tests/test_stable_rows.py
+enumerates all 4^9 neighbourhoods (the set is exactly what they produce) and
+runs the kernels on a batch that presents every row of it
+(tests/stable_rows.py covering_batch)."""
 from __future__ import annotations
 
 import os
