@@ -137,6 +137,54 @@ struct alignas(64) LifeState {
   }
   LifeState Moved(std::pair<int, int> v) const { return Moved(v.first, v.second); }
 
+  // ---- the per-offset questions, CPU, single universe; batches go to the
+  // GPU via lifeapi::MatchBatch / ConvolveBatch / InteractionOffsetsBatch.
+  // With s(x, y) = bit y of column x and indices mod 64:
+  // Mirrored() (LifeAPI.hpp:789-795): cell (x, y) -> (-x, -y)
+  LifeState Mirrored() const {
+    LifeState r(InitializedTag::UNINITIALIZED);
+    for (int i = 0; i < N; ++i) {
+      uint64_t v = state[i];  // bit y -> bit 63 - y, then up one row: -y
+      v = (v >> 1 & 0x5555555555555555ULL) | (v & 0x5555555555555555ULL) << 1;
+      v = (v >> 2 & 0x3333333333333333ULL) | (v & 0x3333333333333333ULL) << 2;
+      v = (v >> 4 & 0x0F0F0F0F0F0F0F0FULL) | (v & 0x0F0F0F0F0F0F0F0FULL) << 4;
+      v = (v >> 8 & 0x00FF00FF00FF00FFULL) | (v & 0x00FF00FF00FF00FFULL) << 8;
+      v = (v >> 16 & 0x0000FFFF0000FFFFULL) | (v & 0x0000FFFF0000FFFFULL) << 16;
+      r.state[torus_wrap(-i)] = std::rotl(v >> 32 | v << 32, 1);
+    }
+    return r;
+  }
+  // Convolve (LifeAPI.hpp:1293-1370): the torus Minkowski sum,
+  // result(x, y) = OR over (a, b) in other of s(x - a, y - b); time
+  // proportional to other's population
+  LifeState Convolve(const LifeState &other) const {
+    LifeState r;
+    for (int a = 0; a < N; ++a)
+      for (uint64_t w = other.state[a]; w; w &= w - 1) {
+        const int b = std::countr_zero(w);
+        for (int i = 0; i < N; ++i) r.state[(i + a) & (N - 1)] |= std::rotl(state[i], b);
+      }
+    return r;
+  }
+  // MatchLive / MatchLiveAndDead (LifeAPI.hpp:427-435): result(x, y) = every
+  // cell (a, b) of live has s(x + a, y + b) = 1 [and every cell of dead has
+  // s(x + a, y + b) = 0]; an empty pattern is vacuously satisfied
+  LifeState MatchLive(const LifeState &live) const { return MatchLiveAndDead(live, LifeState()); }
+  LifeState MatchLiveAndDead(const LifeState &live, const LifeState &dead) const {
+    LifeState all = ~LifeState(), any;
+    for (int a = 0; a < N; ++a) {
+      for (uint64_t w = live.state[a]; w; w &= w - 1)
+        for (int x = 0; x < N; ++x) all.state[x] &= std::rotr(state[(x + a) & (N - 1)], std::countr_zero(w));
+      for (uint64_t w = dead.state[a]; w; w &= w - 1)
+        for (int x = 0; x < N; ++x) any.state[x] |= std::rotr(state[(x + a) & (N - 1)], std::countr_zero(w));
+    }
+    return all & ~any;
+  }
+  // Match (LifeAPI.hpp:440-442): the pattern with its boundary dead
+  LifeState Match(const LifeState &live) const { return MatchLiveAndDead(live, live.GetBoundary()); }
+  inline LifeState Match(const struct LifeTarget &t) const;            // LifeTarget.hpp:53-55
+  inline LifeState InteractionOffsets(const LifeState &other) const;   // LifeAPI.hpp:1066-1095
+
   // ---- bitsliced adders (LifeAPI.hpp:822-833)
   static void HalfAdd(uint64_t &out0, uint64_t &out1, uint64_t a, uint64_t b) {
     out0 = a ^ b;
@@ -353,6 +401,41 @@ struct NeighbourCount {
     return r;
   }
 };
+
+// LifeTarget.hpp:53-55
+inline LifeState LifeState::Match(const LifeTarget &t) const { return MatchLiveAndDead(t.wanted, t.unwanted); }
+
+// LifeAPI.hpp:1066-1095: the offsets at which `other`, moved there, overlaps
+// this pattern or changes its next generation, as the OR of seven
+// convolutions of count planes of this pattern with count planes of
+// other.Mirrored() (count = the inclusive 3x3 count; "dead" = not in the
+// pattern itself):
+//   cells x cells                                    (overlap)
+//   dead with count 1 x dead with count 2, both ways (births)
+//   live with count 3 x dead with count >= 2, and
+//   live with count >= 4 x dead with count >= 1, both ways (overcrowding)
+inline LifeState LifeState::InteractionOffsets(const LifeState &other) const {
+  struct Planes {
+    LifeState cells, dead1, dead2, live3, live4up, dead2up, dead1up;
+    explicit Planes(const LifeState &s) {
+      const NeighbourCount c(s);
+      const LifeState high = c.bit3 | c.bit2, low = ~high;
+      cells = s;
+      dead1 = low & ~c.bit1 & c.bit0 & ~s;
+      dead2 = low & c.bit1 & ~c.bit0 & ~s;
+      live3 = low & c.bit1 & c.bit0 & s;
+      live4up = high & s;
+      dead2up = (high | c.bit1) & ~s;
+      dead1up = (high | c.bit1 | c.bit0) & ~s;
+    }
+  };
+  const Planes a(*this), b(other.Mirrored());
+  // (Convolve is symmetric: each is taken with other's plane as the pattern,
+  // so the time is proportional to other's planes' populations)
+  return a.cells.Convolve(b.cells) | a.dead1.Convolve(b.dead2) | a.dead2.Convolve(b.dead1) |
+         a.live3.Convolve(b.dead2up) | a.live4up.Convolve(b.dead1up) | a.dead2up.Convolve(b.live3) |
+         a.dead1up.Convolve(b.live4up);
+}
 
 // LifeWeld.hpp:18-186 (hot-path subset): a state plus a frozen 3-bit
 // neighbour count added when stepping.

@@ -213,6 +213,41 @@ std::vector<uint8_t> AreDisjointBatch(std::span<const S> in, const P &pat, int d
   return detail::pattern_batch(in, words(&pat), true, dx, dy, device);
 }
 
+// ---- the per-offset questions: where does the target occur, where can a
+// pattern be placed ----
+//
+// out[i] = in[i].Match(target)  (LifeTarget.hpp:53-55 -> MatchLiveAndDead,
+// LifeAPI.hpp:432-435): bit y of column x set iff in[i] contains the target
+// moved by (x, y).  out may be the same array as in.
+template <LifeStateLayout S, LifeTargetLayout T>
+void MatchBatch(std::span<const S> in, const T &target, std::span<S> out, int device = 0) {
+  if (out.size() != in.size()) throw Error(LIFEAPI_E_INVALID, "lifeapi: size mismatch");
+  const uint64_t *t = words(&target);
+  check(lifeapi_match_batch(words(in.data()), t, t + 64, words(out.data()), nullptr, in.size(), device));
+}
+// r[i] = in[i].Match(target).GetPop(): the number of places the target
+// occurs, with no mask brought back
+template <LifeStateLayout S, LifeTargetLayout T>
+std::vector<uint32_t> MatchCountBatch(std::span<const S> in, const T &target, int device = 0) {
+  std::vector<uint32_t> r(in.size());
+  const uint64_t *t = words(&target);
+  check(lifeapi_match_batch(words(in.data()), t, t + 64, nullptr, r.data(), in.size(), device));
+  return r;
+}
+// out[i] = in[i].Convolve(pattern)  (LifeAPI.hpp:1293-1370)
+template <LifeStateLayout S, LifeStateLayout P>
+void ConvolveBatch(std::span<const S> in, const P &pattern, std::span<S> out, int device = 0) {
+  if (out.size() != in.size()) throw Error(LIFEAPI_E_INVALID, "lifeapi: size mismatch");
+  check(lifeapi_convolve_batch(words(in.data()), words(&pattern), words(out.data()), in.size(), device));
+}
+// out[i] = in[i].InteractionOffsets(other)  (LifeAPI.hpp:1066-1095)
+template <LifeStateLayout S, LifeStateLayout P>
+void InteractionOffsetsBatch(std::span<const S> in, const P &other, std::span<S> out, int device = 0) {
+  if (out.size() != in.size()) throw Error(LIFEAPI_E_INVALID, "lifeapi: size mismatch");
+  check(lifeapi_interaction_offsets_batch(words(in.data()), words(&other), words(out.data()), in.size(),
+                                          device));
+}
+
 // The search-loop idiom over a batch, in place (LifeAPI.hpp:1196-1216,
 // LifeTarget.hpp:44-51):
 //     for (unsigned g = 1; g <= gens; ++g) { s.Step(); if (!first && s.Contains(target)) first = g; }

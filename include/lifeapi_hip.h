@@ -12,6 +12,15 @@
  *   lifeapi_pop_batch_dev        LifeState::GetPop()        LifeAPI.hpp:290-298
  *   lifeapi_contains_batch_dev   LifeState::Contains(const LifeTarget&)
  *                                                           LifeTarget.hpp:44-51
+ *   lifeapi_match_batch[_dev]    LifeState::Match(const LifeTarget&)
+ *                                                           LifeTarget.hpp:53-55
+ *                                LifeState::MatchLiveAndDead LifeAPI.hpp:432-435
+ *                                LifeState::MatchLive, Match(const LifeState&)
+ *                                                           LifeAPI.hpp:427-442
+ *   lifeapi_convolve_batch[_dev] LifeState::Convolve        LifeAPI.hpp:1293-1370
+ *                                (ZOI, BigZOI, NZOI are this with a fixed pattern)
+ *   lifeapi_interaction_offsets_batch[_dev]
+ *                                LifeState::InteractionOffsets LifeAPI.hpp:1066-1095
  *   lifeapi_fill_random_dev      LifeState::RandomState()   LifeAPI.hpp:63-69
  *                                (seeded splitmix64; mode 1 = RandomState's
  *                                 [2^61, 2^62) column distribution)
@@ -99,6 +108,23 @@ int lifeapi_step_contains_batch_dev(const uint64_t *d_in, uint64_t *d_final,
                                     const uint64_t *d_wanted, const uint64_t *d_unwanted,
                                     uint32_t *d_first_gen, size_t n, uint32_t generations,
                                     void *stream);
+/* d_out[u] = states[u].Match(LifeTarget{wanted, unwanted}) (LifeTarget.hpp:53-55,
+ * LifeAPI.hpp:432-435): bit y of word x set iff the target moved by (x, y) is
+ * contained.  d_count (may be NULL) receives the number of matches per universe;
+ * d_out may be NULL when d_count is not (nothing but 4 bytes per universe is
+ * written then); both NULL is an error.  An empty plane is vacuously
+ * satisfied; d_out may be d_states.  Time is proportional to the target's
+ * care cells (match_kernels.hpp).                                          */
+int lifeapi_match_batch_dev(const uint64_t *d_states, const uint64_t *d_wanted,
+                            const uint64_t *d_unwanted, uint64_t *d_out, uint32_t *d_count,
+                            size_t n, void *stream);
+/* d_out[u] = states[u].Convolve(pattern) (LifeAPI.hpp:1293-1370); one pattern
+ * of 64 device words for the batch; d_out may be d_states                   */
+int lifeapi_convolve_batch_dev(const uint64_t *d_states, const uint64_t *d_pattern,
+                               uint64_t *d_out, size_t n, void *stream);
+/* d_out[u] = states[u].InteractionOffsets(other) (LifeAPI.hpp:1066-1095)        */
+int lifeapi_interaction_offsets_batch_dev(const uint64_t *d_states, const uint64_t *d_other,
+                                          uint64_t *d_out, size_t n, void *stream);
 /* Inclusive 3x3 neighbourhood count of each universe as 4 planes:
  * d_out = n x {bit3, bit2, bit1, bit0} x 64 words.
  * Replaces NeighbourCount(const LifeState&) (NeighbourCount.hpp:40-70) and
@@ -181,6 +207,14 @@ int lifeapi_interaction_counts_batch(const uint64_t *in, uint64_t *out, size_t n
 int lifeapi_refined_step_batch(const uint64_t *in, uint64_t *out, size_t n, int device);
 int lifeapi_contains_batch(const uint64_t *states, const uint64_t *wanted, const uint64_t *unwanted,
                            uint8_t *out, size_t n, int device);
+/* host forms of the per-offset entry points: out (may equal states) and
+ * count as the *_dev forms take them (lifeapi_match_batch: one may be NULL) */
+int lifeapi_match_batch(const uint64_t *states, const uint64_t *wanted, const uint64_t *unwanted,
+                        uint64_t *out, uint32_t *count, size_t n, int device);
+int lifeapi_convolve_batch(const uint64_t *states, const uint64_t *pattern, uint64_t *out, size_t n,
+                           int device);
+int lifeapi_interaction_offsets_batch(const uint64_t *states, const uint64_t *other, uint64_t *out,
+                                      size_t n, int device);
 /* host form of lifeapi_step_contains_batch_dev: the search-loop idiom
  * "for g in 1..gens: s.Step(); if (s.Contains(target)) ..." (LifeAPI.hpp:
  * 1196-1216, LifeTarget.hpp:44-51) over n host universes; final (may be NULL,

@@ -601,6 +601,54 @@ int lifeapi_contains_batch(const uint64_t *states, const uint64_t *wanted, const
                     });
 }
 
+int lifeapi_match_batch(const uint64_t *states, const uint64_t *wanted, const uint64_t *unwanted,
+                        uint64_t *out, uint32_t *count, size_t n, int device) {
+  if (n == 0) return LIFEAPI_OK;
+  if (!states || !wanted || !unwanted || (!out && !count) || !aligned8(states) || (out && !aligned8(out)))
+    return fail(LIFEAPI_E_INVALID, "bad pointer to lifeapi_match_batch%s");
+  if (out) {
+    const int rc = check_batch(states, out, n);
+    if (rc != LIFEAPI_OK) return rc;
+  }
+  // the states' staging slot doubles as the device mask buffer (in place)
+  const bool mask = out != nullptr, cnt = count != nullptr;
+  return host_batch(n, device,
+                    {{states, out, 512}, {nullptr, count, 4}, {wanted, nullptr, 512, true},
+                     {unwanted, nullptr, 512, true}},
+                    [=](void *const *d, size_t m, hipStream_t s) {
+                      return lifeapi_match_batch_dev((const uint64_t *)d[0], (const uint64_t *)d[2],
+                                                     (const uint64_t *)d[3], mask ? (uint64_t *)d[0] : nullptr,
+                                                     cnt ? (uint32_t *)d[1] : nullptr, m, s);
+                    });
+}
+
+// Convolve / InteractionOffsets with `pattern` the whole-array operand; the
+// states' staging slot doubles as the device output (in place)
+static int pattern_batch(const uint64_t *states, const uint64_t *pattern, uint64_t *out, size_t n, int device,
+                         bool interaction, const char *what) {
+  if (n == 0) return LIFEAPI_OK;
+  if (!pattern) return fail(LIFEAPI_E_INVALID, "null pattern pointer to %s", what);
+  const int rc = check_batch(states, out, n);
+  if (rc != LIFEAPI_OK) return rc;
+  return host_batch(n, device, {{states, out, 512}, {pattern, nullptr, 512, true}},
+                    [=](void *const *d, size_t m, hipStream_t s) {
+                      return interaction
+                                 ? lifeapi_interaction_offsets_batch_dev((const uint64_t *)d[0], (const uint64_t *)d[1],
+                                                                         (uint64_t *)d[0], m, s)
+                                 : lifeapi_convolve_batch_dev((const uint64_t *)d[0], (const uint64_t *)d[1],
+                                                              (uint64_t *)d[0], m, s);
+                    });
+}
+
+int lifeapi_convolve_batch(const uint64_t *states, const uint64_t *pattern, uint64_t *out, size_t n, int device) {
+  return pattern_batch(states, pattern, out, n, device, false, "lifeapi_convolve_batch");
+}
+
+int lifeapi_interaction_offsets_batch(const uint64_t *states, const uint64_t *other, uint64_t *out, size_t n,
+                                      int device) {
+  return pattern_batch(states, other, out, n, device, true, "lifeapi_interaction_offsets_batch");
+}
+
 int lifeapi_step_contains_batch(const uint64_t *in, uint64_t *final_states, const uint64_t *wanted,
                                 const uint64_t *unwanted, uint32_t *first_gen, size_t n,
                                 uint32_t generations, int device) {

@@ -71,6 +71,12 @@ _SIGS = {
     "lifeapi_parse_rle_batch_dev": ([_vp, _vp, _sz, _vp, _vp, _vp], _int),
     "lifeapi_rle_batch": ([_vp, _sz, _vp, _sz, _vp, _int], _int),
     "lifeapi_parse_rle_batch": ([_vp, _vp, _sz, _vp, _vp, _int], _int),
+    "lifeapi_match_batch_dev": ([_vp, _vp, _vp, _vp, _vp, _sz, _vp], _int),
+    "lifeapi_convolve_batch_dev": ([_vp, _vp, _vp, _sz, _vp], _int),
+    "lifeapi_interaction_offsets_batch_dev": ([_vp, _vp, _vp, _sz, _vp], _int),
+    "lifeapi_match_batch": ([_vp, _vp, _vp, _vp, _vp, _sz, _int], _int),
+    "lifeapi_convolve_batch": ([_vp, _vp, _vp, _sz, _int], _int),
+    "lifeapi_interaction_offsets_batch": ([_vp, _vp, _vp, _sz, _int], _int),
 }
 for _name, (_args, _res) in _SIGS.items():
     _f = getattr(lib, _name)
@@ -164,6 +170,55 @@ def contains(states: torch.Tensor, wanted: torch.Tensor, unwanted: torch.Tensor,
     return out
 
 
+def _out_like(states: torch.Tensor, out: torch.Tensor | None, n: int) -> torch.Tensor:
+    if out is None:
+        out = torch.empty_like(states)
+    if _universes(out, "out") != n:
+        raise ValueError("out has a different number of universes")
+    return out
+
+
+def match(states: torch.Tensor, wanted: torch.Tensor, unwanted: torch.Tensor,
+          out: torch.Tensor | None = None, count: bool | str = False, stream=None):
+    """Per-universe ``Match(LifeTarget{wanted, unwanted})`` (LifeTarget.hpp:53-55,
+    LifeAPI.hpp:432-435): the mask of offsets at which the target is contained;
+    ``out`` may be ``states``.  ``count=True`` returns (mask, int32 match
+    counts), ``count="only"`` the counts alone (no mask is written)."""
+    n = _universes(states)
+    _universes(wanted, "wanted"), _universes(unwanted, "unwanted")
+    only = count == "only"
+    if only and out is not None:
+        raise ValueError('count="only" writes no mask: out must be None')
+    mask = None if only else _out_like(states, out, n)
+    counts = torch.empty(n, dtype=torch.int32, device=states.device) if count else None
+    _check(lib.lifeapi_match_batch_dev(states.data_ptr(), wanted.data_ptr(), unwanted.data_ptr(),
+                                       None if only else mask.data_ptr(),
+                                       counts.data_ptr() if count else None, n, _stream(stream)))
+    return counts if only else (mask, counts) if count else mask
+
+
+def convolve(states: torch.Tensor, pattern: torch.Tensor, out: torch.Tensor | None = None,
+             stream=None) -> torch.Tensor:
+    """Per-universe ``Convolve(pattern)`` (LifeAPI.hpp:1293-1370); ``out`` may be ``states``."""
+    n = _universes(states)
+    _universes(pattern, "pattern")
+    out = _out_like(states, out, n)
+    _check(lib.lifeapi_convolve_batch_dev(states.data_ptr(), pattern.data_ptr(), out.data_ptr(), n,
+                                          _stream(stream)))
+    return out
+
+
+def interaction_offsets(states: torch.Tensor, other: torch.Tensor, out: torch.Tensor | None = None,
+                        stream=None) -> torch.Tensor:
+    """Per-universe ``InteractionOffsets(other)`` (LifeAPI.hpp:1066-1095); ``out`` may be ``states``."""
+    n = _universes(states)
+    _universes(other, "other")
+    out = _out_like(states, out, n)
+    _check(lib.lifeapi_interaction_offsets_batch_dev(states.data_ptr(), other.data_ptr(), out.data_ptr(), n,
+                                                     _stream(stream)))
+    return out
+
+
 def step_contains(states: torch.Tensor, wanted: torch.Tensor, unwanted: torch.Tensor,
                   generations: int, final: torch.Tensor | None = None, stream=None):
     """First generation (1..gens, 0 = never) at which each universe contains the target."""
@@ -218,6 +273,38 @@ def step_contains_host(states: np.ndarray, wanted: np.ndarray, unwanted: np.ndar
     _check(lib.lifeapi_step_contains_batch(src.ctypes.data, fptr, w.ctypes.data, u.ctypes.data,
                                            first.ctypes.data, src.size // N, generations, device))
     return first
+
+
+def match_host(states: np.ndarray, wanted: np.ndarray, unwanted: np.ndarray, out: np.ndarray | None = None,
+               count: bool | str = False, device: int = 0):
+    """Host-pointer ``lifeapi_match_batch``; ``out`` and ``count`` as :func:`match`."""
+    src, w, u = _host_u64(states), _host_u64(wanted), _host_u64(unwanted)
+    n, only = src.size // N, count == "only"
+    mask = None if only else (np.empty_like(src) if out is None else out)
+    counts = np.empty(n, dtype=np.uint32) if count else None
+    _check(lib.lifeapi_match_batch(src.ctypes.data, w.ctypes.data, u.ctypes.data,
+                                   None if only else mask.ctypes.data,
+                                   counts.ctypes.data if count else None, n, device))
+    return counts if only else (mask, counts) if count else mask
+
+
+def convolve_host(states: np.ndarray, pattern: np.ndarray, out: np.ndarray | None = None,
+                  device: int = 0) -> np.ndarray:
+    """Host-pointer ``lifeapi_convolve_batch``."""
+    src, p = _host_u64(states), _host_u64(pattern)
+    dst = np.empty_like(src) if out is None else out
+    _check(lib.lifeapi_convolve_batch(src.ctypes.data, p.ctypes.data, dst.ctypes.data, src.size // N, device))
+    return dst
+
+
+def interaction_offsets_host(states: np.ndarray, other: np.ndarray, out: np.ndarray | None = None,
+                             device: int = 0) -> np.ndarray:
+    """Host-pointer ``lifeapi_interaction_offsets_batch``."""
+    src, p = _host_u64(states), _host_u64(other)
+    dst = np.empty_like(src) if out is None else out
+    _check(lib.lifeapi_interaction_offsets_batch(src.ctypes.data, p.ctypes.data, dst.ctypes.data, src.size // N,
+                                                 device))
+    return dst
 
 
 class host_pinned:
