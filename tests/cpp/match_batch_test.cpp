@@ -2,8 +2,13 @@
 // of lifeapi/batch.hpp against the facade's own single-universe CPU members
 // (lifeapi/LifeState.hpp), every universe of a seeded batch.  The Python
 // tests (tests/test_gpu_match.py) pin the GPU entry points to the reference's
-// recorded outputs, so agreement here pins the CPU members too.  Needs a GPU;
-// run by tests/test_gpu_match.py.  Exit status = number of failed checks.
+// recorded outputs, so agreement here pins the CPU members too, on the inputs
+// used here and as far as those inputs tell answers apart: Match on dense
+// soups and on the near misses of two targets (one wrong care cell each),
+// Convolve on sparse soups, InteractionOffsets on dense soups, whose masks
+// are all but full and pin little, and on sparse soups with clusters, whose
+// masks are between 5 % and 95 % full.  Needs a GPU; run by
+// tests/test_gpu_match.py.  Exit status = number of failed checks.
 #include <lifeapi/LifeState.hpp>
 
 #include <cstdio>
@@ -33,6 +38,42 @@ static std::vector<LifeState> Seeded(uint64_t seed) {
     v[i] = LifeState::RandomState(seed);
     if (i & 1) v[i] &= LifeState::RandomState(seed);
   }
+  return v;
+}
+
+// sparse with clusters: a soup of 1/128 density (seven RandomStates ANDed,
+// without the row that RandomState always sets) and two 4 x 4 half-density
+// boxes at seeded places, the first across both seams in every eighth universe
+static std::vector<LifeState> SparseWithClusters(uint64_t seed) {
+  std::vector<LifeState> v(kN);
+  for (size_t i = 0; i < kN; ++i) {
+    LifeState s = LifeState::RandomState(seed);
+    for (int k = 0; k < 6; ++k) s &= LifeState::RandomState(seed);
+    for (int x = 0; x < 64; ++x) s.state[x] &= (uint64_t(1) << 61) - 1;
+    for (int box = 0; box < 2; ++box) {
+      const LifeState r = LifeState::RandomState(seed);
+      unsigned x0 = r.state[0] & 63, y0 = (r.state[0] >> 6) & 63;
+      if (box == 0 && i % 8 == 0) x0 = 62, y0 = 61 + unsigned(i / 8 % 3);
+      for (unsigned c = 0; c < 16; ++c)
+        if ((r.state[1] >> c) & 1) s.Set((x0 + c / 4) & 63, (y0 + c % 4) & 63);
+    }
+    v[i] = s;
+  }
+  return v;
+}
+
+// t.wanted moved by (dx, dy) with all else dead, which matches at (dx, dy),
+// then one universe per care cell of t with that cell alone flipped
+static std::vector<LifeState> NearMisses(const LifeTarget &t, int dx, int dy) {
+  const LifeState base = t.wanted.Moved(dx, dy), care = t.wanted | t.unwanted;
+  std::vector<LifeState> v{base};
+  for (unsigned x = 0; x < 64; ++x)
+    for (unsigned y = 0; y < 64; ++y)
+      if (care.Get(x, y)) {
+        LifeState s = base;
+        s.state[(x + dx) & 63] ^= uint64_t(1) << ((y + dy) & 63);
+        v.push_back(s);
+      }
   return v;
 }
 
@@ -70,6 +111,21 @@ static void MatchBatch_EqualsCpu() {
   std::vector<LifeState> io = in;
   lifeapi::MatchBatch(std::span<const LifeState>(io), Targets()[2], std::span(io));
   for (size_t i = 0; i < kN; ++i) EXPECT_EQ(io[i], in[i].Match(Targets()[2]));
+  // near misses of the block with its ring (moved across both seams) and of
+  // the 3 + 5 care cells: only the first universe matches at the planted offset
+  const int at[2][3] = {{0, 43, 33}, {2, 50, 9}};
+  for (const auto &[k, dx, dy] : at) {
+    const LifeTarget t = Targets()[k];
+    const std::vector<LifeState> miss = NearMisses(t, dx, dy);
+    EXPECT_EQ(miss.size(), size_t(1) + (t.wanted | t.unwanted).GetPop());
+    std::vector<LifeState> got(miss.size());
+    lifeapi::MatchBatch(std::span<const LifeState>(miss), t, std::span(got));
+    for (size_t i = 0; i < miss.size(); ++i) {
+      EXPECT_EQ(got[i], miss[i].Match(t));
+      EXPECT_EQ(got[i].Get(dx, dy), i == 0);
+      EXPECT_EQ(miss[i].Match(t).Get(dx, dy), i == 0);
+    }
+  }
 }
 
 static void ConvolveBatch_EqualsCpu() {
@@ -102,6 +158,20 @@ static void InteractionOffsetsBatch_EqualsCpu() {
   for (const LifeState &o : {eater.Moved(30, 30), eater.Moved(62, 62), LifeState::Parse("bo$2bo$3o!"), LifeState()}) {
     lifeapi::InteractionOffsetsBatch(std::span<const LifeState>(in), o, std::span(out));
     for (size_t i = 0; i < kN; ++i) EXPECT_EQ(out[i], in[i].InteractionOffsets(o));
+  }
+  // sparse universes with clusters: masks that are neither empty nor full, so
+  // that a lost term or a wrong threshold of either side would show.  The
+  // R-pentomino has live cells of inclusive count 3, 4 and 5.
+  in = SparseWithClusters(404);
+  for (const LifeState &o : {eater.Moved(62, 62), LifeState::Parse("b2o$2o$bo!").Moved(62, 62)}) {
+    lifeapi::InteractionOffsetsBatch(std::span<const LifeState>(in), o, std::span(out));
+    size_t mixed = 0;
+    for (size_t i = 0; i < kN; ++i) {
+      const LifeState want = in[i].InteractionOffsets(o);
+      EXPECT_EQ(out[i], want);
+      mixed += want.GetPop() >= 4096 / 20 && want.GetPop() <= 4096 - 4096 / 20;
+    }
+    EXPECT_TRUE(mixed >= kN * 9 / 10);
   }
 }
 

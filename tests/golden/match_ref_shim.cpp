@@ -7,6 +7,9 @@
 // IN:  uint64 n, nt, np, no; states[n][64]; targets[nt][2][64];
 //      patterns[np][64]; others[no][64]
 // OUT: match[nt][n][64]; convolve[np][n][64]; interaction[no][n][64]
+// Any of nt, np, no may be 0: for tests/golden/match_sharp.npz the generator
+// runs this once per target on that target's own near misses, once for the
+// patterns on the impulse states and once for the others on the sparse batch.
 //
 // The same translation unit instantiates the batched templates of
 // lifeapi/batch.hpp on the reference's ::LifeState / ::LifeTarget, so that

@@ -1,7 +1,9 @@
 """GPU: batched Match, Convolve and InteractionOffsets (match_kernels.hpp)
 through lifeapi_amd.hip, bit-exact against (1) the reference's recorded
-outputs (tests/golden/match.npz) and (2) the numpy definitions of
-tests/test_match_model.py, which a CPU test pins to the same fixture."""
+outputs (tests/golden/match.npz, and tests/golden/match_sharp.npz on the
+sharp inputs of tests/match_sharp.py: near misses, impulses, sparse soups
+with clusters) and (2) the numpy definitions of tests/test_match_model.py,
+which CPU tests pin to the same fixtures."""
 import os
 import subprocess
 import sys
@@ -10,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+import match_sharp as S
 import test_match_model as M
 
 pytestmark = pytest.mark.gpu
@@ -117,6 +120,105 @@ def test_ragged_convolve_and_interaction_offsets(hip, ragged, n):
             assert (to_host(fn(s, arg)) == want[key][:n]).all(), (key, offset8)
             assert fn(s, arg, out=s) is s
             assert (to_host(s) == want[key][:n]).all(), (key, offset8, "in place")
+
+
+# ---- the sharp inputs: one wrong cell, one lost term or threshold shows --------
+
+@pytest.fixture(scope="module")
+def sharp(port):
+    return S.fixture_data(port)
+
+
+@pytest.fixture(scope="module")
+def clustered(port, sharp):
+    """interaction_batch(4097) and the numpy definition's answer for every
+    sharp other, computed once; a batch of n is the first n"""
+    x = S.interaction_batch(port, S.N_BATCH)
+    want = {name: M.np_interaction_offsets(x, sharp["others"][k]) for k, name in enumerate(sharp["other_names"])}
+    for k, name in enumerate(sharp["other_names"]):
+        assert (want[name][:S.N_RECORDED] == sharp["interaction"][k]).all()
+    for a in (x, *want.values()):
+        a.flags.writeable = False
+    return x, want
+
+
+@pytest.mark.parametrize("offset8", [False, True])
+def test_near_miss_match(hip, sharp, offset8):
+    """every target on its own near misses against the reference's recorded
+    masks: mask, mask + count, count only, in place.  Universe 0 matches at
+    the planted offset and no near miss does."""
+    for name, (states, (dx, dy), (w, u), want) in sharp["near_miss"].items():
+        dw, du, s = to_dev(w), to_dev(u), to_dev(states, offset8)
+        pops = M.popcount(want)
+        got = to_host(hip.match(s, dw, du))
+        assert (got == want).all(), name
+        hit = (got[:, dx] >> np.uint64(dy)) & M.U1
+        assert hit[0] == 1 and not hit[1:].any(), name
+        mask, count = hip.match(s, dw, du, count=True)
+        assert (to_host(mask) == want).all(), name
+        assert (to_host(count) == pops).all(), name
+        assert (to_host(hip.match(s, dw, du, count="only")) == pops).all(), name
+        assert (to_host(s) == states).all(), name
+        assert hip.match(s, dw, du, out=s) is s
+        assert (to_host(s) == want).all(), (name, "in place")
+
+
+@pytest.mark.parametrize("offset8", [False, True])
+def test_impulse_convolve(hip, sharp, offset8):
+    """every pattern on the single cells and the pair: the answer is the
+    pattern moved, so each of its cells shows"""
+    for k, (name, p) in enumerate(sharp["patterns"].items()):
+        s, dp = to_dev(sharp["impulse_states"], offset8), to_dev(p)
+        assert (to_host(hip.convolve(s, dp)) == sharp["convolve"][k]).all(), name
+        assert hip.convolve(s, dp, out=s) is s
+        assert (to_host(s) == sharp["convolve"][k]).all(), (name, "in place")
+
+
+def test_recorded_interaction_offsets(hip, sharp):
+    s = to_dev(sharp["batch"])
+    for k, name in enumerate(sharp["other_names"]):
+        got = to_host(hip.interaction_offsets(s, to_dev(sharp["others"][k])))
+        assert (got == sharp["interaction"][k]).all(), name
+    assert (to_host(s) == sharp["batch"]).all()
+
+
+@pytest.mark.parametrize("n", RAGGED)
+def test_ragged_clustered_interaction_offsets(hip, sharp, clustered, n):
+    """out of place and in place, 16- and 8-byte aligned, every sharp other"""
+    x, want = clustered
+    for k, name in enumerate(sharp["other_names"]):
+        do = to_dev(sharp["others"][k])
+        for offset8 in (False, True):
+            s = to_dev(x[:n], offset8)
+            assert (to_host(hip.interaction_offsets(s, do)) == want[name][:n]).all(), (name, offset8)
+            assert (to_host(s) == x[:n]).all()
+            assert hip.interaction_offsets(s, do, out=s) is s
+            assert (to_host(s) == want[name][:n]).all(), (name, offset8, "in place")
+
+
+def test_clustered_interaction_offsets_side_stream(hip, sharp, clustered):
+    x, want = clustered
+    side = torch.cuda.Stream()
+    s = to_dev(x)
+    others = [to_dev(o) for o in sharp["others"]]
+    torch.cuda.synchronize()
+    with torch.cuda.stream(side):
+        got = [hip.interaction_offsets(s, do, stream=side) for do in others]
+    side.synchronize()
+    for name, g in zip(sharp["other_names"], got):
+        assert (to_host(g) == want[name]).all(), name
+
+
+@pytest.mark.parametrize("device,shards", [(0, None), (-1, 3)])
+def test_clustered_interaction_offsets_host_forms(hip, sharp, clustered, monkeypatch, device, shards):
+    if shards:
+        monkeypatch.setenv("LIFEAPI_HOST_SHARDS", str(shards))
+    x, want = clustered
+    for k, name in enumerate(sharp["other_names"]):
+        assert (hip.interaction_offsets_host(x, sharp["others"][k], device=device) == want[name]).all(), name
+    y = x.copy()
+    assert hip.interaction_offsets_host(y, sharp["others"][0], out=y, device=device) is y
+    assert (y == want[sharp["other_names"][0]]).all()
 
 
 # ---- counts -------------------------------------------------------------------
@@ -227,8 +329,9 @@ def test_host_forms(hip, ragged, monkeypatch, device, shards):
 
 def test_match_batch_cpp():
     """tests/cpp/match_batch_test.cpp: MatchBatch / MatchCountBatch /
-    ConvolveBatch / InteractionOffsetsBatch on 1000 seeded states against the
-    facade's own CPU members"""
+    ConvolveBatch / InteractionOffsetsBatch on 1000 seeded states, dense and
+    sparse with clusters, and on near misses, against the facade's own CPU
+    members"""
     exe = os.path.join(ROOT, "build", "match_batch_test")
     if not os.path.exists(exe):
         import __graft_entry__ as g
