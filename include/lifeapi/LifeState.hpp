@@ -17,6 +17,7 @@
 #include <cstdint>
 #include <string>
 #include <utility>
+#include <vector>
 
 namespace lifeapi {
 
@@ -25,6 +26,72 @@ inline constexpr int N = 64;  // LifeAPI.hpp:12
 constexpr unsigned torus_wrap(int x) { return unsigned(x) & (N - 1); }  // LifeAPI.hpp:14-16
 
 enum class InitializedTag { UNINITIALIZED };  // LifeAPI.hpp:37
+
+// Symmetry.hpp:7-26.  Each is an affine map of the torus; the "Even" forms
+// reflect about a line between cells, the others fix (0, 0):
+//   Identity (x, y)                  Rotate180OddBoth        (-x, -y)
+//   ReflectAcrossXEven (x, -y-1)     Rotate180EvenHorizontal (-x-1, -y)
+//   ReflectAcrossX     (x, -y)       Rotate180EvenVertical   (-x, -y-1)
+//   ReflectAcrossYEven (-x-1, y)     Rotate180EvenBoth       (-x-1, -y-1)
+//   ReflectAcrossY     (-x, y)       ReflectAcrossYeqX       (y, x)
+//   Rotate90Even  (-y-1, x)          ReflectAcrossYeqNegX    (-y-1, -x-1)
+//   Rotate90      (-y, x)            ReflectAcrossYeqNegXP1  (-y, -x)
+//   Rotate270Even (y, -x-1)          Rotate270               (y, -x)
+enum struct SymmetryTransform : uint32_t {
+  Identity,
+  ReflectAcrossXEven,
+  ReflectAcrossX,
+  ReflectAcrossYEven,
+  ReflectAcrossY,
+  Rotate90Even,
+  Rotate90,
+  Rotate270Even,
+  Rotate270,
+  Rotate180OddBoth,
+  Rotate180EvenHorizontal,
+  Rotate180EvenVertical,
+  Rotate180EvenBoth,
+  ReflectAcrossYeqX,
+  ReflectAcrossYeqNegX,
+  ReflectAcrossYeqNegXP1
+};
+
+// Symmetry.hpp:47-55: the two pairs of quarter turns; every other transform
+// is its own inverse
+inline SymmetryTransform TransformInverse(SymmetryTransform t) {
+  switch (t) {
+  case SymmetryTransform::Rotate90Even: return SymmetryTransform::Rotate270Even;
+  case SymmetryTransform::Rotate90: return SymmetryTransform::Rotate270;
+  case SymmetryTransform::Rotate270Even: return SymmetryTransform::Rotate90Even;
+  case SymmetryTransform::Rotate270: return SymmetryTransform::Rotate90;
+  default: return t;
+  }
+}
+
+// Symmetry.hpp:57-79
+enum struct StaticSymmetry : uint32_t {
+  C1,
+  D2AcrossX,
+  D2AcrossXEven,
+  D2AcrossY,
+  D2AcrossYEven,
+  D2negdiagodd,
+  D2diagodd,
+  C2,
+  C2even,
+  C2verticaleven,
+  C2horizontaleven,
+  C4,
+  C4even,
+  D4,
+  D4even,
+  D4verticaleven,
+  D4horizontaleven,
+  D4diag,
+  D4diageven,
+  D8,
+  D8even,
+};
 
 struct alignas(64) LifeState {
   uint64_t state[N];
@@ -136,6 +203,89 @@ struct alignas(64) LifeState {
     return r;
   }
   LifeState Moved(std::pair<int, int> v) const { return Moved(v.first, v.second); }
+
+  // ---- the symmetry layer (LifeAPI.hpp:446-484,754-806, Symmetry.hpp:105-173,
+  // 798-830), CPU, single universe; batches go to the GPU via
+  // lifeapi::TransformBatch / SymmetricizeBatch / XYBoundsBatch /
+  // SymmetryOrbitBatch.
+  // FlipY: cell (x, y) -> (-x - 1, y); FlipX = BitReverse: (x, y) -> (x, -y - 1)
+  void FlipY() {
+    for (int i = 0; i < N / 2; ++i) std::swap(state[i], state[N - 1 - i]);
+  }
+  void BitReverse() {
+    for (int i = 0; i < N; ++i) {
+      uint64_t v = state[i];
+      v = (v >> 1 & 0x5555555555555555ULL) | (v & 0x5555555555555555ULL) << 1;
+      v = (v >> 2 & 0x3333333333333333ULL) | (v & 0x3333333333333333ULL) << 2;
+      v = (v >> 4 & 0x0F0F0F0F0F0F0F0FULL) | (v & 0x0F0F0F0F0F0F0F0FULL) << 4;
+      v = (v >> 8 & 0x00FF00FF00FF00FFULL) | (v & 0x00FF00FF00FF00FFULL) << 8;
+      v = (v >> 16 & 0x0000FFFF0000FFFFULL) | (v & 0x0000FFFF0000FFFFULL) << 16;
+      state[i] = v >> 32 | v << 32;
+    }
+  }
+  void FlipX() { BitReverse(); }
+  // Transpose(false): (x, y) -> (y, x), six rounds of block exchanges (rows
+  // with bit j set of column k against rows with bit j clear of column k | j);
+  // Transpose(true): (x, y) -> (-y - 1, -x - 1), the same between flips
+  void Transpose(bool whichDiagonal) {
+    uint64_t m = 0x00000000FFFFFFFFULL;
+    for (int j = N / 2; j; j >>= 1, m ^= m << j)
+      for (int k = 0; k < N; ++k)
+        if (!(k & j)) {
+          const uint64_t t = ((state[k] >> j) ^ state[k | j]) & m;
+          state[k] ^= t << j;
+          state[k | j] ^= t;
+        }
+    if (whichDiagonal) {
+      FlipX();
+      FlipY();
+    }
+  }
+  void Transpose() { Transpose(true); }
+  void Transform(SymmetryTransform t) {
+    using enum SymmetryTransform;
+    const bool flipx = t == ReflectAcrossXEven || t == ReflectAcrossX || t == Rotate90Even || t == Rotate90 ||
+                       (t >= Rotate180OddBoth && t <= Rotate180EvenBoth);
+    const bool flipy = t == ReflectAcrossYEven || t == ReflectAcrossY || t == Rotate270Even || t == Rotate270 ||
+                       (t >= Rotate180OddBoth && t <= Rotate180EvenBoth);
+    if (flipx) FlipX();
+    if (flipy) FlipY();
+    if (t >= Rotate90Even && t <= Rotate270) Transpose(false);
+    if (t == ReflectAcrossYeqX) Transpose(false);
+    if (t == ReflectAcrossYeqNegX || t == ReflectAcrossYeqNegXP1) Transpose(true);
+    const bool right = t == ReflectAcrossY || t == Rotate90 || t == Rotate180OddBoth || t == Rotate180EvenVertical ||
+                       t == ReflectAcrossYeqNegXP1;
+    const bool down = t == ReflectAcrossX || t == Rotate270 || t == Rotate180OddBoth ||
+                      t == Rotate180EvenHorizontal || t == ReflectAcrossYeqNegXP1;
+    if (right || down) Move(right, down);
+  }
+  LifeState Transformed(SymmetryTransform t) const {
+    LifeState r = *this;
+    r.Transform(t);
+    return r;
+  }
+  // (LifeAPI.hpp:803-806: the move comes first)
+  void Transform(int dx, int dy, SymmetryTransform t) {
+    Move(dx, dy);
+    Transform(t);
+  }
+  // {left, top, right, bottom} in the window of columns and rows -32 .. 31
+  // (LifeAPI.hpp:446-484); an empty state gives -1 four times.  A pattern
+  // straddling the window's edge is reported as the reference reports it.
+  std::array<int, 4> XYBounds() const {
+    uint64_t cols = 0, rows = 0;
+    for (int i = 0; i < N; ++i) {
+      cols |= uint64_t(state[i] != 0) << i;
+      rows |= state[i];
+    }
+    if (rows == 0) return {-1, -1, -1, -1};
+    cols = std::rotr(cols, 32);
+    rows = std::rotr(rows, 32);
+    return {std::countr_zero(cols) - 32, std::countr_zero(rows) - 32, 31 - std::countl_zero(cols),
+            31 - std::countl_zero(rows)};
+  }
+  inline std::vector<LifeState> SymmetryOrbit() const;
+  inline std::vector<SymmetryTransform> SymmetryOrbitRepresentatives() const;
 
   // ---- the per-offset questions, CPU, single universe; batches go to the
   // GPU via lifeapi::MatchBatch / ConvolveBatch / InteractionOffsetsBatch.
@@ -348,7 +498,90 @@ struct alignas(64) LifeState {
 
 static_assert(sizeof(LifeState) == 512 && alignof(LifeState) == 64, "LifeAPI.hpp:39-40 layout");
 
-// LifeTarget.hpp:5-36 (the search-loop subset; no Transform)
+// Symmetry.hpp:798-830: the eight images under D4, each moved so that its
+// bounds start at (0, 0), those equal to an earlier one dropped; and the
+// transforms that gave the ones kept
+namespace detail {
+inline constexpr SymmetryTransform kOrbit[8] = {
+    SymmetryTransform::Identity,          SymmetryTransform::ReflectAcrossX,
+    SymmetryTransform::ReflectAcrossYeqX, SymmetryTransform::ReflectAcrossY,
+    SymmetryTransform::ReflectAcrossYeqNegXP1, SymmetryTransform::Rotate90,
+    SymmetryTransform::Rotate270,         SymmetryTransform::Rotate180OddBoth};
+inline void orbit(const LifeState &s, std::vector<LifeState> &images, std::vector<SymmetryTransform> &kept) {
+  for (SymmetryTransform t : kOrbit) {
+    LifeState img = s.Transformed(t);
+    const std::array<int, 4> b = img.XYBounds();
+    img.Move(-b[0], -b[1]);
+    bool seen = false;
+    for (const LifeState &e : images) seen = seen || e == img;
+    if (!seen) {
+      images.push_back(img);
+      kept.push_back(t);
+    }
+  }
+}
+}  // namespace detail
+inline std::vector<LifeState> LifeState::SymmetryOrbit() const {
+  std::vector<LifeState> images;
+  std::vector<SymmetryTransform> kept;
+  detail::orbit(*this, images, kept);
+  return images;
+}
+inline std::vector<SymmetryTransform> LifeState::SymmetryOrbitRepresentatives() const {
+  std::vector<LifeState> images;
+  std::vector<SymmetryTransform> kept;
+  detail::orbit(*this, images, kept);
+  return kept;
+}
+
+// Symmetry.hpp:540-563: the part of `offset` across the transform's mirror
+// line.  The diagonal cases halve in int arithmetic, truncating as C++ does,
+// so the result is not a function of the offset mod 64 alone.
+inline std::pair<int, int> PerpComponent(SymmetryTransform t, std::pair<int, int> offset) {
+  const int x = (offset.first + 32) % 64 - 32, y = (offset.second + 32) % 64 - 32;
+  switch (t) {
+  case SymmetryTransform::ReflectAcrossX: return {0, offset.second};
+  case SymmetryTransform::ReflectAcrossY: return {offset.first, 0};
+  case SymmetryTransform::ReflectAcrossYeqX: return {((x - y + 128) / 2) % 64, ((-x + y + 128) / 2) % 64};
+  case SymmetryTransform::ReflectAcrossYeqNegXP1: return {((x + y + 128) / 2) % 64, ((x + y + 128) / 2) % 64};
+  default: return offset;
+  }
+}
+
+// Symmetry.hpp:565-654: the union of `state` with its images under the
+// symmetry's generators, the mirror lines / centre displaced by `offset`.
+// Defined for the nine symmetries below, as in the reference.
+inline LifeState Symmetricize(const LifeState &state, StaticSymmetry sym, std::pair<int, int> offset) {
+  using enum SymmetryTransform;
+  const auto [dx, dy] = offset;
+  // acc | acc.Transformed(t).Moved(mx, my)
+  auto with = [](const LifeState &acc, SymmetryTransform t, int mx, int my) {
+    return acc | acc.Transformed(t).Moved(mx, my);
+  };
+  switch (sym) {
+  case StaticSymmetry::C1: return state;
+  case StaticSymmetry::C2: return with(state, Rotate180EvenBoth, dx + 1, dy + 1);
+  case StaticSymmetry::C4:
+    return with(with(state, Rotate90, dx, dy), Rotate180EvenBoth, dx - dy + 1, dy + dx + 1);
+  case StaticSymmetry::D2AcrossX: return with(state, ReflectAcrossXEven, dx, dy + 1);
+  case StaticSymmetry::D2AcrossY: return with(state, ReflectAcrossYEven, dx + 1, dy);
+  case StaticSymmetry::D2diagodd: return with(state, ReflectAcrossYeqX, dx, dy);
+  case StaticSymmetry::D2negdiagodd: return with(state, ReflectAcrossYeqNegX, dx + 1, dy + 1);
+  case StaticSymmetry::D4: {
+    const auto xo = PerpComponent(ReflectAcrossX, offset), yo = PerpComponent(ReflectAcrossY, offset);
+    return with(with(state, ReflectAcrossXEven, xo.first, xo.second + 1), ReflectAcrossYEven, yo.first + 1,
+                yo.second);
+  }
+  case StaticSymmetry::D4diag: {
+    const auto yo = PerpComponent(ReflectAcrossYeqX, offset), xo = PerpComponent(ReflectAcrossYeqNegXP1, offset);
+    return with(with(state, ReflectAcrossYeqX, yo.first, yo.second), ReflectAcrossYeqNegX, xo.first + 1,
+                xo.second + 1);
+  }
+  default: __builtin_unreachable();
+  }
+}
+
+// LifeTarget.hpp:5-36 (the search-loop subset)
 struct LifeTarget {
   LifeState wanted;
   LifeState unwanted;
@@ -358,6 +591,13 @@ struct LifeTarget {
   LifeTarget(const LifeState &w, const LifeState &u) : wanted(w), unwanted(u) {}
   LifeTarget Moved(std::pair<int, int> v) const {  // :33-35
     return LifeTarget(wanted.Moved(v), unwanted.Moved(v));
+  }
+  void Transform(SymmetryTransform t) {  // :20-23
+    wanted.Transform(t);
+    unwanted.Transform(t);
+  }
+  LifeTarget Transformed(SymmetryTransform t) const {  // :26-30
+    return LifeTarget(wanted.Transformed(t), unwanted.Transformed(t));
   }
 };
 

@@ -14,12 +14,14 @@
 // return value, see lifeapi_hip.h).  Link with -llifeapi_hip.
 #pragma once
 
+#include <array>
 #include <bit>
 #include <cstdint>
 #include <span>
 #include <stdexcept>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../lifeapi_hip.h"
@@ -246,6 +248,70 @@ void InteractionOffsetsBatch(std::span<const S> in, const P &other, std::span<S>
   if (out.size() != in.size()) throw Error(LIFEAPI_E_INVALID, "lifeapi: size mismatch");
   check(lifeapi_interaction_offsets_batch(words(in.data()), words(&other), words(out.data()), in.size(),
                                           device));
+}
+
+// ---- the symmetry layer (Symmetry.hpp) ----
+//
+// T is a SymmetryTransform and Y a StaticSymmetry: the reference's own enums
+// or lifeapi's (the same enumerators in the same order), or their values.
+//
+// out[i] = in[i].Transformed(t)  (Symmetry.hpp:105-173); out may be in
+template <LifeStateLayout S, class T>
+void TransformBatch(std::span<const S> in, std::span<S> out, T t, int device = 0) {
+  if (out.size() != in.size()) throw Error(LIFEAPI_E_INVALID, "lifeapi: size mismatch");
+  check(lifeapi_transform_batch(words(in.data()), words(out.data()), in.size(), static_cast<uint32_t>(t), 0, 0,
+                                device));
+}
+// out[i] = in[i] after Transform(dx, dy, t)  (LifeAPI.hpp:803-806): Move(dx, dy)
+// FIRST, then Transform(t).  With t's linear part A that is Transform(t) then
+// Move(A (dx, dy)), which is the one launch the library has.
+template <LifeStateLayout S, class T>
+void TransformBatch(std::span<const S> in, std::span<S> out, int dx, int dy, T t, int device = 0) {
+  if (out.size() != in.size()) throw Error(LIFEAPI_E_INVALID, "lifeapi: size mismatch");
+  const uint32_t v = static_cast<uint32_t>(t);
+  if (v > 15) throw Error(LIFEAPI_E_INVALID, "lifeapi: no such SymmetryTransform");
+  // per transform: 1 = the axes are exchanged, 2 = x negated, 4 = y negated
+  // (A (x, y) = (+-x, +-y), or (+-y, +-x) with the signs on the result's x, y)
+  static constexpr uint8_t kLinear[16] = {0, 4, 4, 2, 2, 3, 3, 5, 5, 6, 6, 6, 6, 1, 7, 7};
+  const long long x = dx & 63, y = dy & 63;  // (Move wraps)
+  const long long ax = (kLinear[v] & 1) ? y : x, ay = (kLinear[v] & 1) ? x : y;
+  check(lifeapi_transform_batch(words(in.data()), words(out.data()), in.size(), v,
+                                (int)((kLinear[v] & 2) ? -ax : ax), (int)((kLinear[v] & 4) ? -ay : ay), device));
+}
+// out[i] = Symmetricize(in[i], sym, offset)  (Symmetry.hpp:565-654); out may be in
+template <LifeStateLayout S, class Y>
+void SymmetricizeBatch(std::span<const S> in, std::span<S> out, Y sym, std::pair<int, int> offset, int device = 0) {
+  if (out.size() != in.size()) throw Error(LIFEAPI_E_INVALID, "lifeapi: size mismatch");
+  check(lifeapi_symmetricize_batch(words(in.data()), words(out.data()), in.size(), static_cast<uint32_t>(sym),
+                                   offset.first, offset.second, device));
+}
+// r[i] = in[i].XYBounds()  (LifeAPI.hpp:446-484)
+template <LifeStateLayout S>
+std::vector<std::array<int, 4>> XYBoundsBatch(std::span<const S> in, int device = 0) {
+  static_assert(sizeof(std::array<int, 4>) == 4 * sizeof(int32_t));
+  std::vector<std::array<int, 4>> r(in.size());
+  check(lifeapi_bounds_batch(words(in.data()), reinterpret_cast<int32_t *>(r.data()), in.size(), device));
+  return r;
+}
+// SymmetryOrbit's eight transforms in its order (Symmetry.hpp:801-803), as
+// SymmetryTransform values: bit i of a mask below stands for kOrbitTransforms[i]
+inline constexpr uint32_t kOrbitTransforms[8] = {0, 2, 13, 4, 15, 6, 8, 9};
+// r[i] = the mask of in[i].SymmetryOrbitRepresentatives()  (Symmetry.hpp:814-830)
+template <LifeStateLayout S>
+std::vector<uint8_t> SymmetryOrbitRepresentativesBatch(std::span<const S> in, int device = 0) {
+  std::vector<uint8_t> r(in.size());
+  check(lifeapi_symmetry_orbit_batch(words(in.data()), nullptr, r.data(), in.size(), device));
+  return r;
+}
+// images[8 i + k] = in[i].Transformed(kOrbitTransforms[k]) moved by minus its
+// bounds' (left, top); returns the masks: in[i].SymmetryOrbit()
+// (Symmetry.hpp:798-812) is the images of mask i's set bits, in order
+template <LifeStateLayout S>
+std::vector<uint8_t> SymmetryOrbitBatch(std::span<const S> in, std::span<S> images, int device = 0) {
+  if (images.size() != 8 * in.size()) throw Error(LIFEAPI_E_INVALID, "lifeapi: size mismatch");
+  std::vector<uint8_t> r(in.size());
+  check(lifeapi_symmetry_orbit_batch(words(in.data()), words(images.data()), r.data(), in.size(), device));
+  return r;
 }
 
 // The search-loop idiom over a batch, in place (LifeAPI.hpp:1196-1216,

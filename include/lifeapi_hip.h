@@ -21,6 +21,16 @@
  *                                (ZOI, BigZOI, NZOI are this with a fixed pattern)
  *   lifeapi_interaction_offsets_batch[_dev]
  *                                LifeState::InteractionOffsets LifeAPI.hpp:1066-1095
+ *   lifeapi_transform_batch[_dev] LifeState::Transform, Transformed
+ *                                                           Symmetry.hpp:105-173
+ *                                LifeState::Move, Moved, FlipX, FlipY,
+ *                                Transpose, Mirrored        LifeAPI.hpp:682-806
+ *   lifeapi_symmetricize_batch[_dev] Symmetricize, PerpComponent
+ *                                                           Symmetry.hpp:540-654
+ *   lifeapi_bounds_batch[_dev]   LifeState::XYBounds        LifeAPI.hpp:446-484
+ *   lifeapi_symmetry_orbit_batch[_dev]
+ *                                LifeState::SymmetryOrbit, SymmetryOrbitRepresentatives
+ *                                                           Symmetry.hpp:798-830
  *   lifeapi_fill_random_dev      LifeState::RandomState()   LifeAPI.hpp:63-69
  *                                (seeded splitmix64; mode 1 = RandomState's
  *                                 [2^61, 2^62) column distribution)
@@ -125,6 +135,35 @@ int lifeapi_convolve_batch_dev(const uint64_t *d_states, const uint64_t *d_patte
 /* d_out[u] = states[u].InteractionOffsets(other) (LifeAPI.hpp:1066-1095)        */
 int lifeapi_interaction_offsets_batch_dev(const uint64_t *d_states, const uint64_t *d_other,
                                           uint64_t *d_out, size_t n, void *stream);
+/* d_out[u] = d_in[u].Transformed(transform).Moved(dx, dy)
+ * (Symmetry.hpp:105-173, LifeAPI.hpp:682-735).
+ * transform: the SymmetryTransform's value, 0..15 (Symmetry.hpp:7-26).
+ * dx, dy: any int (Move wraps).
+ * With transform 0 this is Moved; 1 FlipX; 3 FlipY; 13 / 14 Transpose(false / true).
+ * Rotate180OddBoth (9) is Mirrored.  d_out may be d_in.                     */
+int lifeapi_transform_batch_dev(const uint64_t *d_in, uint64_t *d_out, size_t n, uint32_t transform,
+                                int dx, int dy, void *stream);
+/* d_out[u] = Symmetricize(d_in[u], symmetry, {dx, dy}) (Symmetry.hpp:565-654).
+ * symmetry: the StaticSymmetry's value (Symmetry.hpp:57-79): C1 0, D2AcrossX 1,
+ * D2AcrossY 3, D2negdiagodd 5, D2diagodd 6, C2 7, C4 11, D4 13, D4diag 17.
+ * LIFEAPI_E_INVALID for the symmetries the reference leaves undefined.
+ * d_out may be d_in.                                                        */
+int lifeapi_symmetricize_batch_dev(const uint64_t *d_in, uint64_t *d_out, size_t n, uint32_t symmetry,
+                                   int dx, int dy, void *stream);
+/* d_bounds[4u .. 4u+3] = d_states[u].XYBounds() (LifeAPI.hpp:446-484):
+ * {left, top, right, bottom} in the window [-32, 31], -1 four times for an
+ * empty state                                                              */
+int lifeapi_bounds_batch_dev(const uint64_t *d_states, int32_t *d_bounds, size_t n, void *stream);
+/* SymmetryOrbit / SymmetryOrbitRepresentatives (Symmetry.hpp:798-830).
+ * d_images (may be NULL): n x 8 x 64 words, image i = Transformed(t_i) moved by
+ *   minus its XYBounds' (left, top), t_i in the reference's order: Identity,
+ *   ReflectAcrossX, ReflectAcrossYeqX, ReflectAcrossY, ReflectAcrossYeqNegXP1,
+ *   Rotate90, Rotate270, Rotate180OddBoth.
+ * d_first (may be NULL): bit i of d_first[u] is set iff image i equals no earlier
+ *   image.  The set bits are the representatives; their images are SymmetryOrbit().
+ * Both NULL is an error.  No output may overlap the input.                  */
+int lifeapi_symmetry_orbit_batch_dev(const uint64_t *d_states, uint64_t *d_images, uint8_t *d_first,
+                                     size_t n, void *stream);
 /* Inclusive 3x3 neighbourhood count of each universe as 4 planes:
  * d_out = n x {bit3, bit2, bit1, bit0} x 64 words.
  * Replaces NeighbourCount(const LifeState&) (NeighbourCount.hpp:40-70) and
@@ -215,6 +254,15 @@ int lifeapi_convolve_batch(const uint64_t *states, const uint64_t *pattern, uint
                            int device);
 int lifeapi_interaction_offsets_batch(const uint64_t *states, const uint64_t *other, uint64_t *out,
                                       size_t n, int device);
+/* host forms of the symmetry entry points: out may equal in; images and
+ * first as lifeapi_symmetry_orbit_batch_dev takes them (one may be NULL)   */
+int lifeapi_transform_batch(const uint64_t *in, uint64_t *out, size_t n, uint32_t transform, int dx, int dy,
+                            int device);
+int lifeapi_symmetricize_batch(const uint64_t *in, uint64_t *out, size_t n, uint32_t symmetry, int dx,
+                               int dy, int device);
+int lifeapi_bounds_batch(const uint64_t *states, int32_t *bounds, size_t n, int device);
+int lifeapi_symmetry_orbit_batch(const uint64_t *states, uint64_t *images, uint8_t *first, size_t n,
+                                 int device);
 /* host form of lifeapi_step_contains_batch_dev: the search-loop idiom
  * "for g in 1..gens: s.Step(); if (s.Contains(target)) ..." (LifeAPI.hpp:
  * 1196-1216, LifeTarget.hpp:44-51) over n host universes; final (may be NULL,

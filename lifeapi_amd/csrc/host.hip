@@ -649,6 +649,49 @@ int lifeapi_interaction_offsets_batch(const uint64_t *states, const uint64_t *ot
   return pattern_batch(states, other, out, n, device, true, "lifeapi_interaction_offsets_batch");
 }
 
+// the symmetry layer; Transform and Symmetricize run in place on the states'
+// staging slot
+int lifeapi_transform_batch(const uint64_t *in, uint64_t *out, size_t n, uint32_t transform, int dx, int dy,
+                            int device) {
+  const int rc = check_batch(in, out, n);
+  if (rc != LIFEAPI_OK || n == 0) return rc;
+  return host_batch(n, device, {{in, out, 512}}, [=](void *const *d, size_t m, hipStream_t s) {
+    return lifeapi_transform_batch_dev((const uint64_t *)d[0], (uint64_t *)d[0], m, transform, dx, dy, s);
+  });
+}
+
+int lifeapi_symmetricize_batch(const uint64_t *in, uint64_t *out, size_t n, uint32_t symmetry, int dx, int dy,
+                               int device) {
+  const int rc = check_batch(in, out, n);
+  if (rc != LIFEAPI_OK || n == 0) return rc;
+  return host_batch(n, device, {{in, out, 512}}, [=](void *const *d, size_t m, hipStream_t s) {
+    return lifeapi_symmetricize_batch_dev((const uint64_t *)d[0], (uint64_t *)d[0], m, symmetry, dx, dy, s);
+  });
+}
+
+int lifeapi_bounds_batch(const uint64_t *states, int32_t *bounds, size_t n, int device) {
+  if (n == 0) return LIFEAPI_OK;
+  if (!states || !bounds || !aligned8(states)) return fail(LIFEAPI_E_INVALID, "bad pointer to lifeapi_bounds_batch%s");
+  return host_batch(n, device, {{states, nullptr, 512}, {nullptr, bounds, 16}},
+                    [](void *const *d, size_t m, hipStream_t s) {
+                      return lifeapi_bounds_batch_dev((const uint64_t *)d[0], (int32_t *)d[1], m, s);
+                    });
+}
+
+int lifeapi_symmetry_orbit_batch(const uint64_t *states, uint64_t *images, uint8_t *first, size_t n, int device) {
+  if (n == 0) return LIFEAPI_OK;
+  if (!states || (!images && !first) || !aligned8(states) || (images && !aligned8(images)))
+    return fail(LIFEAPI_E_INVALID, "bad pointer to lifeapi_symmetry_orbit_batch%s");
+  // (an output the caller leaves out keeps a one-byte slot and is not copied)
+  const bool img = images != nullptr, fst = first != nullptr;
+  return host_batch(n, device, {{states, nullptr, 512}, {nullptr, images, img ? size_t(8 * 512) : size_t(1)}, {nullptr, first, 1}},
+                    [=](void *const *d, size_t m, hipStream_t s) {
+                      return lifeapi_symmetry_orbit_batch_dev((const uint64_t *)d[0],
+                                                              img ? (uint64_t *)d[1] : nullptr,
+                                                              fst ? (uint8_t *)d[2] : nullptr, m, s);
+                    });
+}
+
 int lifeapi_step_contains_batch(const uint64_t *in, uint64_t *final_states, const uint64_t *wanted,
                                 const uint64_t *unwanted, uint32_t *first_gen, size_t n,
                                 uint32_t generations, int device) {

@@ -77,6 +77,14 @@ _SIGS = {
     "lifeapi_match_batch": ([_vp, _vp, _vp, _vp, _vp, _sz, _int], _int),
     "lifeapi_convolve_batch": ([_vp, _vp, _vp, _sz, _int], _int),
     "lifeapi_interaction_offsets_batch": ([_vp, _vp, _vp, _sz, _int], _int),
+    "lifeapi_transform_batch_dev": ([_vp, _vp, _sz, _u32, _int, _int, _vp], _int),
+    "lifeapi_symmetricize_batch_dev": ([_vp, _vp, _sz, _u32, _int, _int, _vp], _int),
+    "lifeapi_bounds_batch_dev": ([_vp, _vp, _sz, _vp], _int),
+    "lifeapi_symmetry_orbit_batch_dev": ([_vp, _vp, _vp, _sz, _vp], _int),
+    "lifeapi_transform_batch": ([_vp, _vp, _sz, _u32, _int, _int, _int], _int),
+    "lifeapi_symmetricize_batch": ([_vp, _vp, _sz, _u32, _int, _int, _int], _int),
+    "lifeapi_bounds_batch": ([_vp, _vp, _sz, _int], _int),
+    "lifeapi_symmetry_orbit_batch": ([_vp, _vp, _vp, _sz, _int], _int),
 }
 for _name, (_args, _res) in _SIGS.items():
     _f = getattr(lib, _name)
@@ -219,6 +227,68 @@ def interaction_offsets(states: torch.Tensor, other: torch.Tensor, out: torch.Te
     return out
 
 
+# SymmetryTransform and StaticSymmetry values (Symmetry.hpp:7-26, 57-79), the
+# reference's enumerators in the reference's order
+TRANSFORMS = ("Identity", "ReflectAcrossXEven", "ReflectAcrossX", "ReflectAcrossYEven", "ReflectAcrossY",
+              "Rotate90Even", "Rotate90", "Rotate270Even", "Rotate270", "Rotate180OddBoth",
+              "Rotate180EvenHorizontal", "Rotate180EvenVertical", "Rotate180EvenBoth", "ReflectAcrossYeqX",
+              "ReflectAcrossYeqNegX", "ReflectAcrossYeqNegXP1")
+SYMMETRIES = ("C1", "D2AcrossX", "D2AcrossXEven", "D2AcrossY", "D2AcrossYEven", "D2negdiagodd", "D2diagodd", "C2",
+              "C2even", "C2verticaleven", "C2horizontaleven", "C4", "C4even", "D4", "D4even", "D4verticaleven",
+              "D4horizontaleven", "D4diag", "D4diageven", "D8", "D8even")
+# the transforms of SymmetryOrbit's eight images, in its order (Symmetry.hpp:801-803)
+ORBIT_TRANSFORMS = (0, 2, 13, 4, 15, 6, 8, 9)
+
+
+def _enum(v: int | str, names: tuple) -> int:
+    return names.index(v) if isinstance(v, str) else int(v)
+
+
+def transform(states: torch.Tensor, t: int | str, dx: int = 0, dy: int = 0, out: torch.Tensor | None = None,
+              stream=None) -> torch.Tensor:
+    """Per-universe ``Transformed(t).Moved(dx, dy)`` (Symmetry.hpp:105-173,
+    LifeAPI.hpp:682-735); ``t`` a SymmetryTransform's value or name; ``out`` may be ``states``."""
+    n = _universes(states)
+    out = _out_like(states, out, n)
+    _check(lib.lifeapi_transform_batch_dev(states.data_ptr(), out.data_ptr(), n, _enum(t, TRANSFORMS), dx, dy,
+                                           _stream(stream)))
+    return out
+
+
+def symmetricize(states: torch.Tensor, symmetry: int | str, dx: int = 0, dy: int = 0,
+                 out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+    """Per-universe ``Symmetricize(state, symmetry, {dx, dy})`` (Symmetry.hpp:565-654);
+    ``symmetry`` a StaticSymmetry's value or name; ``out`` may be ``states``."""
+    n = _universes(states)
+    out = _out_like(states, out, n)
+    _check(lib.lifeapi_symmetricize_batch_dev(states.data_ptr(), out.data_ptr(), n, _enum(symmetry, SYMMETRIES),
+                                              dx, dy, _stream(stream)))
+    return out
+
+
+def bounds(states: torch.Tensor, stream=None) -> torch.Tensor:
+    """Per-universe ``XYBounds()`` (LifeAPI.hpp:446-484): (n, 4) int32 {left, top, right, bottom}."""
+    n = _universes(states)
+    out = torch.empty((n, 4), dtype=torch.int32, device=states.device)
+    _check(lib.lifeapi_bounds_batch_dev(states.data_ptr(), out.data_ptr(), n, _stream(stream)))
+    return out
+
+
+def symmetry_orbit(states: torch.Tensor, images: bool = True, first: bool = True, stream=None):
+    """Per-universe ``SymmetryOrbit`` / ``SymmetryOrbitRepresentatives``
+    (Symmetry.hpp:798-830): the (n, 8, 64) normalised images in the order of
+    ORBIT_TRANSFORMS and / or the uint8 mask whose bit i is set iff image i
+    equals no earlier one (the set bits' images are the orbit)."""
+    n = _universes(states)
+    if not (images or first):
+        raise ValueError("symmetry_orbit: nothing asked for")
+    img = torch.empty((n, 8, N), dtype=torch.int64, device=states.device) if images else None
+    fst = torch.empty(n, dtype=torch.uint8, device=states.device) if first else None
+    _check(lib.lifeapi_symmetry_orbit_batch_dev(states.data_ptr(), img.data_ptr() if images else None,
+                                                fst.data_ptr() if first else None, n, _stream(stream)))
+    return (img, fst) if images and first else img if images else fst
+
+
 def step_contains(states: torch.Tensor, wanted: torch.Tensor, unwanted: torch.Tensor,
                   generations: int, final: torch.Tensor | None = None, stream=None):
     """First generation (1..gens, 0 = never) at which each universe contains the target."""
@@ -305,6 +375,47 @@ def interaction_offsets_host(states: np.ndarray, other: np.ndarray, out: np.ndar
     _check(lib.lifeapi_interaction_offsets_batch(src.ctypes.data, p.ctypes.data, dst.ctypes.data, src.size // N,
                                                  device))
     return dst
+
+
+def transform_host(states: np.ndarray, t: int | str, dx: int = 0, dy: int = 0, out: np.ndarray | None = None,
+                   device: int = 0) -> np.ndarray:
+    """Host-pointer ``lifeapi_transform_batch``."""
+    src = _host_u64(states)
+    dst = np.empty_like(src) if out is None else out
+    _check(lib.lifeapi_transform_batch(src.ctypes.data, dst.ctypes.data, src.size // N, _enum(t, TRANSFORMS), dx, dy,
+                                       device))
+    return dst
+
+
+def symmetricize_host(states: np.ndarray, symmetry: int | str, dx: int = 0, dy: int = 0,
+                      out: np.ndarray | None = None, device: int = 0) -> np.ndarray:
+    """Host-pointer ``lifeapi_symmetricize_batch``."""
+    src = _host_u64(states)
+    dst = np.empty_like(src) if out is None else out
+    _check(lib.lifeapi_symmetricize_batch(src.ctypes.data, dst.ctypes.data, src.size // N,
+                                          _enum(symmetry, SYMMETRIES), dx, dy, device))
+    return dst
+
+
+def bounds_host(states: np.ndarray, device: int = 0) -> np.ndarray:
+    """Host-pointer ``lifeapi_bounds_batch``: (n, 4) int32."""
+    src = _host_u64(states)
+    out = np.empty((src.size // N, 4), dtype=np.int32)
+    _check(lib.lifeapi_bounds_batch(src.ctypes.data, out.ctypes.data, src.size // N, device))
+    return out
+
+
+def symmetry_orbit_host(states: np.ndarray, images: bool = True, first: bool = True, device: int = 0):
+    """Host-pointer ``lifeapi_symmetry_orbit_batch``; results as :func:`symmetry_orbit`."""
+    src = _host_u64(states)
+    n = src.size // N
+    if not (images or first):
+        raise ValueError("symmetry_orbit_host: nothing asked for")
+    img = np.empty((n, 8, N), dtype=np.uint64) if images else None
+    fst = np.empty(n, dtype=np.uint8) if first else None
+    _check(lib.lifeapi_symmetry_orbit_batch(src.ctypes.data, img.ctypes.data if images else None,
+                                            fst.ctypes.data if first else None, n, device))
+    return (img, fst) if images and first else img if images else fst
 
 
 class host_pinned:
