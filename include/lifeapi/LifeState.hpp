@@ -15,6 +15,7 @@
 #include <array>
 #include <bit>
 #include <cstdint>
+#include <stdexcept>
 #include <string>
 #include <utility>
 #include <vector>
@@ -316,6 +317,62 @@ struct alignas(64) LifeState {
       }
     return r;
   }
+  // ---- connected components, CPU, single universe; batches go to the GPU
+  // via lifeapi::FirstOn / ComponentContaining / ComponentCounts / Components.
+  // FirstOn (LifeAPI.hpp:301-323): the LAST group of four columns that is not
+  // empty, in it the lowest non-empty column, in that column the lowest set
+  // row; (-1, -1) for the empty state
+  std::pair<int, int> FirstOn() const {
+    int quad = 0;
+    for (int x = 0; x < N; x += 4)
+      if (state[x] | state[x + 1] | state[x + 2] | state[x + 3]) quad = x;
+    for (int x = quad; x < quad + 4; ++x)
+      if (state[x]) return {x, std::countr_zero(state[x])};
+    return {-1, -1};
+  }
+  // FirstCell (LifeAPI.hpp:358); the empty state for the empty state, where the
+  // reference sets cell (-1, -1) of nothing
+  LifeState FirstCell() const {
+    const std::pair<int, int> c = FirstOn();
+    return c.first < 0 ? LifeState() : Cell(c);
+  }
+  // the reference's default corona, b3o$5o$5o$5o$b3o! at (-2, -2)
+  // (LifeAPI.hpp:1185-1186): the 21 cells with |a|, |b| <= 2 and |a| + |b| < 4
+  static LifeState DefaultCorona() {
+    LifeState c;
+    for (int a = -2; a <= 2; ++a)
+      for (int b = -2; b <= 2; ++b)
+        if ((a < 0 ? -a : a) + (b < 0 ? -b : b) < 4) c.SetSafe(a, b, true);
+    return c;
+  }
+  // ComponentContaining (LifeAPI.hpp:655-665, 1184-1188): with
+  // N(t) = t.Convolve(corona) & *this, the least R with R = N(seed) | N(R)
+  LifeState ComponentContaining(const LifeState &seed, const LifeState &corona) const {
+    LifeState result, tocheck = seed;
+    while (!tocheck.IsEmpty()) {
+      const LifeState neighbours = tocheck.Convolve(corona) & *this;
+      tocheck = neighbours & ~result;
+      result |= neighbours;
+    }
+    return result;
+  }
+  LifeState ComponentContaining(const LifeState &seed) const { return ComponentContaining(seed, DefaultCorona()); }
+  // Components (LifeAPI.hpp:667-676, 1189-1193), in FirstCell's order.  The
+  // reference does not terminate on a corona without cell (0, 0) (the seed's
+  // component is empty, nothing is ever removed); this throws instead.
+  std::vector<LifeState> Components(const LifeState &corona) const {
+    if (!corona.Get(0, 0)) throw std::invalid_argument("lifeapi: Components needs a corona containing cell (0, 0)");
+    std::vector<LifeState> result;
+    LifeState remaining = *this;
+    while (!remaining.IsEmpty()) {
+      const LifeState component = remaining.ComponentContaining(remaining.FirstCell(), corona);
+      result.push_back(component);
+      remaining &= ~component;
+    }
+    return result;
+  }
+  std::vector<LifeState> Components() const { return Components(DefaultCorona()); }
+
   // MatchLive / MatchLiveAndDead (LifeAPI.hpp:427-435): result(x, y) = every
   // cell (a, b) of live has s(x + a, y + b) = 1 [and every cell of dead has
   // s(x + a, y + b) = 0]; an empty pattern is vacuously satisfied

@@ -314,6 +314,93 @@ std::vector<uint8_t> SymmetryOrbitBatch(std::span<const S> in, std::span<S> imag
   return r;
 }
 
+// ---- connected components (LifeAPI.hpp:301-323, 655-676, 1184-1193) ----
+//
+// A corona is any LifeState-layout value; the overloads without one use the
+// reference's default (b3o$5o$5o$5o$b3o! at (-2, -2)).
+//
+// r[i] = in[i].FirstOn()  (LifeAPI.hpp:301-323); (-1, -1) for the empty state
+template <LifeStateLayout S>
+std::vector<std::pair<int, int>> FirstOn(std::span<const S> in, int device = 0) {
+  std::vector<int32_t> cells(2 * in.size());
+  check(lifeapi_first_on_batch(words(in.data()), cells.data(), in.size(), device));
+  std::vector<std::pair<int, int>> r(in.size());
+  for (size_t i = 0; i < in.size(); ++i) r[i] = {cells[2 * i], cells[2 * i + 1]};
+  return r;
+}
+namespace detail {
+template <LifeStateLayout S>
+std::vector<S> component_containing(std::span<const S> states, const S *seeds, bool per, const uint64_t *corona,
+                                    int device) {
+  std::vector<S> out(states.size());
+  check(lifeapi_component_containing_batch(words(states.data()), words(seeds), per, corona, words(out.data()),
+                                           states.size(), device));
+  return out;
+}
+template <LifeStateLayout S>
+std::vector<uint32_t> component_counts(std::span<const S> states, const uint64_t *corona, int device) {
+  std::vector<uint32_t> counts(states.size());
+  check(lifeapi_components_batch(words(states.data()), corona, counts.data(), nullptr, 0, states.size(), device));
+  return counts;
+}
+// the counts first, then one call sized by their maximum
+template <LifeStateLayout S>
+std::vector<std::vector<S>> components(std::span<const S> states, const uint64_t *corona, int device) {
+  const std::vector<uint32_t> counts = component_counts(states, corona, device);
+  uint32_t cap = 0;
+  for (uint32_t c : counts) cap = c > cap ? c : cap;
+  std::vector<std::vector<S>> r(states.size());
+  if (cap == 0) return r;
+  std::vector<S> flat(states.size() * size_t(cap));
+  check(lifeapi_components_batch(words(states.data()), corona, nullptr, words(flat.data()), cap, states.size(),
+                                 device));
+  for (size_t i = 0; i < states.size(); ++i)
+    r[i].assign(flat.begin() + i * size_t(cap), flat.begin() + i * size_t(cap) + counts[i]);
+  return r;
+}
+}  // namespace detail
+// r[i] = states[i].ComponentContaining(seed[, corona])  (LifeAPI.hpp:655-665, 1184-1188): one seed for the batch
+template <LifeStateLayout S>
+std::vector<S> ComponentContaining(std::span<const S> states, const S &seed, int device = 0) {
+  return detail::component_containing(states, &seed, false, nullptr, device);
+}
+template <LifeStateLayout S, LifeStateLayout C>
+std::vector<S> ComponentContaining(std::span<const S> states, const S &seed, const C &corona, int device = 0) {
+  return detail::component_containing(states, &seed, false, words(&corona), device);
+}
+// r[i] = states[i].ComponentContaining(seeds[i][, corona])
+template <LifeStateLayout S>
+std::vector<S> ComponentContaining(std::span<const S> states, std::span<const S> seeds, int device = 0) {
+  if (seeds.size() != states.size()) throw Error(LIFEAPI_E_INVALID, "lifeapi: size mismatch");
+  return detail::component_containing(states, seeds.data(), true, nullptr, device);
+}
+template <LifeStateLayout S, LifeStateLayout C>
+std::vector<S> ComponentContaining(std::span<const S> states, std::span<const S> seeds, const C &corona,
+                                   int device = 0) {
+  if (seeds.size() != states.size()) throw Error(LIFEAPI_E_INVALID, "lifeapi: size mismatch");
+  return detail::component_containing(states, seeds.data(), true, words(&corona), device);
+}
+// r[i] = states[i].Components([corona]).size()  (LifeAPI.hpp:667-676), with no component brought back
+template <LifeStateLayout S>
+std::vector<uint32_t> ComponentCounts(std::span<const S> states, int device = 0) {
+  return detail::component_counts(states, nullptr, device);
+}
+template <LifeStateLayout S, LifeStateLayout C>
+std::vector<uint32_t> ComponentCounts(std::span<const S> states, const C &corona, int device = 0) {
+  return detail::component_counts(states, words(&corona), device);
+}
+// r[i] = states[i].Components([corona])  (LifeAPI.hpp:667-676, 1189-1193), in
+// the reference's order.  The corona must contain cell (0, 0) (the reference
+// does not terminate otherwise): lifeapi::Error with LIFEAPI_E_INVALID.
+template <LifeStateLayout S>
+std::vector<std::vector<S>> Components(std::span<const S> states, int device = 0) {
+  return detail::components(states, nullptr, device);
+}
+template <LifeStateLayout S, LifeStateLayout C>
+std::vector<std::vector<S>> Components(std::span<const S> states, const C &corona, int device = 0) {
+  return detail::components(states, words(&corona), device);
+}
+
 // The search-loop idiom over a batch, in place (LifeAPI.hpp:1196-1216,
 // LifeTarget.hpp:44-51):
 //     for (unsigned g = 1; g <= gens; ++g) { s.Step(); if (!first && s.Contains(target)) first = g; }

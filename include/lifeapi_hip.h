@@ -31,6 +31,11 @@
  *   lifeapi_symmetry_orbit_batch[_dev]
  *                                LifeState::SymmetryOrbit, SymmetryOrbitRepresentatives
  *                                                           Symmetry.hpp:798-830
+ *   lifeapi_first_on_batch[_dev] LifeState::FirstOn, FirstCell LifeAPI.hpp:301-323, 358
+ *   lifeapi_component_containing_batch[_dev]
+ *                                LifeState::ComponentContaining
+ *                                                           LifeAPI.hpp:655-665, 1184-1188
+ *   lifeapi_components_batch[_dev] LifeState::Components    LifeAPI.hpp:667-676, 1189-1193
  *   lifeapi_fill_random_dev      LifeState::RandomState()   LifeAPI.hpp:63-69
  *                                (seeded splitmix64; mode 1 = RandomState's
  *                                 [2^61, 2^62) column distribution)
@@ -164,6 +169,48 @@ int lifeapi_bounds_batch_dev(const uint64_t *d_states, int32_t *d_bounds, size_t
  * Both NULL is an error.  No output may overlap the input.                  */
 int lifeapi_symmetry_orbit_batch_dev(const uint64_t *d_states, uint64_t *d_images, uint8_t *d_first,
                                      size_t n, void *stream);
+/* d_cells[2u], d_cells[2u+1] = d_states[u].FirstOn() (LifeAPI.hpp:301-323), the
+ * cell FirstCell() holds (LifeAPI.hpp:358) and Components() starts each piece
+ * from: the LAST group of four columns (x = 0, 4, .., 60) that is not empty, in
+ * it the lowest non-empty column, in that column the lowest set row; (-1, -1)
+ * for the empty state.                                                      */
+int lifeapi_first_on_batch_dev(const uint64_t *d_states, int32_t *d_cells, size_t n, void *stream);
+/* d_out[u] = d_states[u].ComponentContaining(seed_u, corona) (LifeAPI.hpp:655-665):
+ * with N(t) = t.Convolve(corona) & state, the least R with R = N(seed) | N(R).
+ * So a seed cell outside the state is not in the result, a seed next to a
+ * component returns that component, an empty seed or corona gives the empty
+ * state, and a corona without (0, 0) may drop the seed.
+ * d_seeds: 64 words (per_universe_seeds == 0, one seed for the batch) or n x 64.
+ * corona: a HOST pointer to 64 words, read before the call returns; NULL = the
+ *   reference's default b3o$5o$5o$5o$b3o! at (-2, -2) (LifeAPI.hpp:1185-1186).
+ *   It is the one argument of a _dev call that is not a device pointer: it is
+ *   checked before anything is launched and goes to the kernel by value, so
+ *   the call owns no staging buffer whose lifetime a stream would have to
+ *   guard.  The default corona, the 3 x 3 block and the 5-cell plus (centred)
+ *   have networks of their own; any other corona costs time in proportion to
+ *   its cells.
+ * d_out may be d_states, or d_seeds when per-universe; any other overlap is
+ * rejected.                                                                 */
+int lifeapi_component_containing_batch_dev(const uint64_t *d_states, const uint64_t *d_seeds,
+                                           int per_universe_seeds, const uint64_t *corona,
+                                           uint64_t *d_out, size_t n, void *stream);
+/* d_states[u].Components(corona) (LifeAPI.hpp:667-676): until nothing remains,
+ * the component of FirstCell() of what remains, which is then removed.
+ * corona: as above (a HOST pointer, NULL = the default).  It must contain cell
+ *   (0, 0): without it the reference's loop never ends, and this call returns
+ *   LIFEAPI_E_INVALID.
+ * d_count (may be NULL): d_count[u] = the true number of components.
+ * d_components (may be NULL): n x max_components x 64 words; component
+ *   i < min(count, max_components) of universe u at ((u * max_components) + i) * 64,
+ *   in the reference's order.  Slots from count up to max_components are not
+ *   written.  A caller that needs every component asks for the counts first
+ *   and sizes a second call by their maximum; one that expects few passes a
+ *   small cap and reads count > cap as "truncated".
+ * Both NULL, or d_components with max_components == 0, is an error.  No output
+ * may overlap the input.                                                    */
+int lifeapi_components_batch_dev(const uint64_t *d_states, const uint64_t *corona, uint32_t *d_count,
+                                 uint64_t *d_components, uint32_t max_components, size_t n,
+                                 void *stream);
 /* Inclusive 3x3 neighbourhood count of each universe as 4 planes:
  * d_out = n x {bit3, bit2, bit1, bit0} x 64 words.
  * Replaces NeighbourCount(const LifeState&) (NeighbourCount.hpp:40-70) and
@@ -263,6 +310,16 @@ int lifeapi_symmetricize_batch(const uint64_t *in, uint64_t *out, size_t n, uint
 int lifeapi_bounds_batch(const uint64_t *states, int32_t *bounds, size_t n, int device);
 int lifeapi_symmetry_orbit_batch(const uint64_t *states, uint64_t *images, uint8_t *first, size_t n,
                                  int device);
+/* host forms of the connected-component entry points: the same arguments
+ * (corona a host pointer there too); out may equal states, or seeds when
+ * per-universe; components is read as well as written, so that the slots past
+ * a universe's count keep the caller's bytes                                */
+int lifeapi_first_on_batch(const uint64_t *states, int32_t *cells, size_t n, int device);
+int lifeapi_component_containing_batch(const uint64_t *states, const uint64_t *seeds,
+                                       int per_universe_seeds, const uint64_t *corona, uint64_t *out,
+                                       size_t n, int device);
+int lifeapi_components_batch(const uint64_t *states, const uint64_t *corona, uint32_t *count,
+                             uint64_t *components, uint32_t max_components, size_t n, int device);
 /* host form of lifeapi_step_contains_batch_dev: the search-loop idiom
  * "for g in 1..gens: s.Step(); if (s.Contains(target)) ..." (LifeAPI.hpp:
  * 1196-1216, LifeTarget.hpp:44-51) over n host universes; final (may be NULL,

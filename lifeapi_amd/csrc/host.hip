@@ -692,6 +692,59 @@ int lifeapi_symmetry_orbit_batch(const uint64_t *states, uint64_t *images, uint8
                     });
 }
 
+// the connected-component family; the corona stays a host pointer all the way
+// to the *_dev call, which reads it before it returns
+int lifeapi_first_on_batch(const uint64_t *states, int32_t *cells, size_t n, int device) {
+  if (n == 0) return LIFEAPI_OK;
+  if (!states || !cells || !aligned8(states)) return fail(LIFEAPI_E_INVALID, "bad pointer to lifeapi_first_on_batch%s");
+  return host_batch(n, device, {{states, nullptr, 512}, {nullptr, cells, 8}},
+                    [](void *const *d, size_t m, hipStream_t s) {
+                      return lifeapi_first_on_batch_dev((const uint64_t *)d[0], (int32_t *)d[1], m, s);
+                    });
+}
+
+int lifeapi_component_containing_batch(const uint64_t *states, const uint64_t *seeds, int per_universe_seeds,
+                                       const uint64_t *corona, uint64_t *out, size_t n, int device) {
+  if (n == 0) return LIFEAPI_OK;
+  int rc = check_batch(states, out, n);
+  if (rc != LIFEAPI_OK) return rc;
+  if (!seeds || !aligned8(seeds))
+    return fail(LIFEAPI_E_INVALID, "null or misaligned seeds pointer to %s", "lifeapi_component_containing_batch");
+  if (per_universe_seeds) {
+    if ((rc = check_batch(seeds, out, n)) != LIFEAPI_OK) return rc;
+  } else if (ranges_overlap(seeds, 512, out, n * 512)) {
+    return fail(LIFEAPI_E_INVALID, "lifeapi_component_containing_batch: the seed overlaps the output batch%s");
+  }
+  // the states' staging slot doubles as the device output (in place)
+  const bool per = per_universe_seeds != 0;
+  return host_batch(n, device, {{states, out, 512}, {seeds, nullptr, 512, !per}},
+                    [=](void *const *d, size_t m, hipStream_t s) {
+                      return lifeapi_component_containing_batch_dev((const uint64_t *)d[0], (const uint64_t *)d[1], per,
+                                                                    corona, (uint64_t *)d[0], m, s);
+                    });
+}
+
+int lifeapi_components_batch(const uint64_t *states, const uint64_t *corona, uint32_t *count, uint64_t *components,
+                             uint32_t max_components, size_t n, int device) {
+  // the argument checks that need no device, in the *_dev call's order
+  const int rc = lifeapi_components_batch_dev(nullptr, corona, nullptr, nullptr, 0, 0, nullptr);
+  if (rc != LIFEAPI_OK || n == 0) return rc;
+  if (!states || (!count && !components) || !aligned8(states) || (components && !aligned8(components)) ||
+      (components && max_components == 0))
+    return fail(LIFEAPI_E_INVALID, "bad argument to lifeapi_components_batch%s");
+  // (an output the caller leaves out keeps a one-byte slot and is not copied;
+  // the components go in as well as out, so that the slots past a universe's
+  // count come back as the caller left them)
+  const bool cnt = count != nullptr, cmp = components != nullptr;
+  return host_batch(n, device,
+                    {{states, nullptr, 512}, {nullptr, count, cnt ? size_t(4) : size_t(1)},
+                     {components, components, cmp ? size_t(max_components) * 512 : size_t(1)}},
+                    [=](void *const *d, size_t m, hipStream_t s) {
+                      return lifeapi_components_batch_dev((const uint64_t *)d[0], corona, cnt ? (uint32_t *)d[1] : nullptr,
+                                                          cmp ? (uint64_t *)d[2] : nullptr, max_components, m, s);
+                    });
+}
+
 int lifeapi_step_contains_batch(const uint64_t *in, uint64_t *final_states, const uint64_t *wanted,
                                 const uint64_t *unwanted, uint32_t *first_gen, size_t n,
                                 uint32_t generations, int device) {

@@ -85,6 +85,12 @@ _SIGS = {
     "lifeapi_symmetricize_batch": ([_vp, _vp, _sz, _u32, _int, _int, _int], _int),
     "lifeapi_bounds_batch": ([_vp, _vp, _sz, _int], _int),
     "lifeapi_symmetry_orbit_batch": ([_vp, _vp, _vp, _sz, _int], _int),
+    "lifeapi_first_on_batch_dev": ([_vp, _vp, _sz, _vp], _int),
+    "lifeapi_component_containing_batch_dev": ([_vp, _vp, _int, _vp, _vp, _sz, _vp], _int),
+    "lifeapi_components_batch_dev": ([_vp, _vp, _vp, _vp, _u32, _sz, _vp], _int),
+    "lifeapi_first_on_batch": ([_vp, _vp, _sz, _int], _int),
+    "lifeapi_component_containing_batch": ([_vp, _vp, _int, _vp, _vp, _sz, _int], _int),
+    "lifeapi_components_batch": ([_vp, _vp, _vp, _vp, _u32, _sz, _int], _int),
 }
 for _name, (_args, _res) in _SIGS.items():
     _f = getattr(lib, _name)
@@ -289,6 +295,74 @@ def symmetry_orbit(states: torch.Tensor, images: bool = True, first: bool = True
     return (img, fst) if images and first else img if images else fst
 
 
+def _corona(corona) -> np.ndarray | None:
+    """The corona as the 64 host words the C ABI reads before it returns
+    (None = the reference's default); a device tensor is brought to the host."""
+    if corona is None:
+        return None
+    if isinstance(corona, torch.Tensor):
+        corona = corona.cpu().numpy()
+    c = np.ascontiguousarray(corona).view(np.uint64).reshape(-1)
+    if c.size != N:
+        raise ValueError("corona must be one universe of 64 words")
+    return c
+
+
+def first_on(states: torch.Tensor, stream=None) -> torch.Tensor:
+    """Per-universe ``FirstOn()`` (LifeAPI.hpp:301-323): (n, 2) int32 {x, y}, the
+    cell ``FirstCell()`` holds; (-1, -1) for the empty state."""
+    n = _universes(states)
+    out = torch.empty((n, 2), dtype=torch.int32, device=states.device)
+    _check(lib.lifeapi_first_on_batch_dev(states.data_ptr(), out.data_ptr(), n, _stream(stream)))
+    return out
+
+
+def component_containing(states: torch.Tensor, seeds: torch.Tensor, corona=None, out: torch.Tensor | None = None,
+                         stream=None) -> torch.Tensor:
+    """Per-universe ``ComponentContaining(seed, corona)`` (LifeAPI.hpp:655-665).
+    ``seeds`` holds one universe (the seed of the whole batch) or one per
+    universe, told apart by its size (for a batch of one the two are the same
+    thing); ``corona`` is host data (None = the reference's default); ``out`` may
+    be ``states``, or ``seeds`` when per-universe."""
+    n = _universes(states)
+    k = _universes(seeds, "seeds")
+    if k != 1 and k != n:
+        raise ValueError("seeds must hold one universe or one per universe")
+    out = _out_like(states, out, n)
+    c = _corona(corona)
+    _check(lib.lifeapi_component_containing_batch_dev(states.data_ptr(), seeds.data_ptr(), int(k == n),
+                                                      None if c is None else c.ctypes.data, out.data_ptr(), n,
+                                                      _stream(stream)))
+    return out
+
+
+def components(states: torch.Tensor, corona=None, max_components: int | None = None, count: bool = True,
+               components_out: torch.Tensor | None = None, stream=None):
+    """Per-universe ``Components(corona)`` (LifeAPI.hpp:667-676).  With
+    ``max_components`` None only the int32 counts come back; otherwise the
+    (n, max_components, 64) components in the reference's order, of which the
+    first min(count, max_components) slots of a universe are written (the rest
+    keep what ``components_out`` held, or are uninitialised), and with
+    ``count`` the pair (components, counts).  The count is always the true
+    one: count > max_components says the list was cut."""
+    n = _universes(states)
+    if max_components is None and not count:
+        raise ValueError("components: nothing asked for")
+    comps = None
+    if max_components is not None:
+        comps = components_out if components_out is not None else torch.empty(
+            (n, max_components, N), dtype=torch.int64, device=states.device)
+        if _universes(comps, "components_out") != n * max_components:
+            raise ValueError("components_out must hold n x max_components universes")
+    counts = torch.empty(n, dtype=torch.int32, device=states.device) if count else None
+    c = _corona(corona)
+    _check(lib.lifeapi_components_batch_dev(states.data_ptr(), None if c is None else c.ctypes.data,
+                                            counts.data_ptr() if count else None,
+                                            None if comps is None else comps.data_ptr(), max_components or 0, n,
+                                            _stream(stream)))
+    return counts if comps is None else (comps, counts) if count else comps
+
+
 def step_contains(states: torch.Tensor, wanted: torch.Tensor, unwanted: torch.Tensor,
                   generations: int, final: torch.Tensor | None = None, stream=None):
     """First generation (1..gens, 0 = never) at which each universe contains the target."""
@@ -416,6 +490,46 @@ def symmetry_orbit_host(states: np.ndarray, images: bool = True, first: bool = T
     _check(lib.lifeapi_symmetry_orbit_batch(src.ctypes.data, img.ctypes.data if images else None,
                                             fst.ctypes.data if first else None, n, device))
     return (img, fst) if images and first else img if images else fst
+
+
+def first_on_host(states: np.ndarray, device: int = 0) -> np.ndarray:
+    """Host-pointer ``lifeapi_first_on_batch``: (n, 2) int32."""
+    src = _host_u64(states)
+    out = np.empty((src.size // N, 2), dtype=np.int32)
+    _check(lib.lifeapi_first_on_batch(src.ctypes.data, out.ctypes.data, src.size // N, device))
+    return out
+
+
+def component_containing_host(states: np.ndarray, seeds: np.ndarray, corona=None, out: np.ndarray | None = None,
+                              device: int = 0) -> np.ndarray:
+    """Host-pointer ``lifeapi_component_containing_batch``; ``seeds`` and ``out`` as :func:`component_containing`."""
+    src, sd = _host_u64(states), _host_u64(seeds)
+    n = src.size // N
+    if sd.size != N and sd.size != src.size:
+        raise ValueError("seeds must hold one universe or one per universe")
+    dst = np.empty_like(src) if out is None else out
+    c = _corona(corona)
+    _check(lib.lifeapi_component_containing_batch(src.ctypes.data, sd.ctypes.data, int(sd.size == src.size),
+                                                  None if c is None else c.ctypes.data, dst.ctypes.data, n, device))
+    return dst
+
+
+def components_host(states: np.ndarray, corona=None, max_components: int | None = None, count: bool = True,
+                    components_out: np.ndarray | None = None, device: int = 0):
+    """Host-pointer ``lifeapi_components_batch``; results as :func:`components`."""
+    src = _host_u64(states)
+    n = src.size // N
+    if max_components is None and not count:
+        raise ValueError("components_host: nothing asked for")
+    comps = None
+    if max_components is not None:
+        comps = np.empty((n, max_components, N), dtype=np.uint64) if components_out is None else components_out
+    counts = np.empty(n, dtype=np.uint32) if count else None
+    c = _corona(corona)
+    _check(lib.lifeapi_components_batch(src.ctypes.data, None if c is None else c.ctypes.data,
+                                        counts.ctypes.data if count else None,
+                                        None if comps is None else comps.ctypes.data, max_components or 0, n, device))
+    return counts if comps is None else (comps, counts) if count else comps
 
 
 class host_pinned:
