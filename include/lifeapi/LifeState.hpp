@@ -734,8 +734,53 @@ inline LifeState LifeState::InteractionOffsets(const LifeState &other) const {
          a.dead1up.Convolve(b.live4up);
 }
 
-// LifeWeld.hpp:18-186 (hot-path subset): a state plus a frozen 3-bit
-// neighbour count added when stepping.
+// LifeStable.hpp:41-53: the ten planes of the stable-search state (options
+// stored as "1 = ruled out").  Propagation runs on the GPU:
+// lifeapi::PropagateStepBatch / PropagateBatch in lifeapi/batch.hpp.
+enum class StableOptions : unsigned char {  // LifeStable.hpp:7-20
+  LIVE2 = 1 << 0, LIVE3 = 1 << 1,
+  DEAD0 = 1 << 2, DEAD1 = 1 << 3, DEAD2 = 1 << 4, DEAD4 = 1 << 5, DEAD5 = 1 << 6, DEAD6 = 1 << 7,
+  IMPOSSIBLE = 0, LIVE = LIVE2 | LIVE3, DEAD = DEAD0 | DEAD1 | DEAD2 | DEAD4 | DEAD5 | DEAD6,
+};
+constexpr StableOptions operator~(StableOptions a) { return StableOptions((unsigned char)~(unsigned char)a); }
+constexpr StableOptions operator|(StableOptions a, StableOptions b) {
+  return StableOptions((unsigned char)a | (unsigned char)b);
+}
+constexpr StableOptions operator&(StableOptions a, StableOptions b) {
+  return StableOptions((unsigned char)a & (unsigned char)b);
+}
+
+struct LifeStable {
+  LifeState state, unknown;
+  LifeState live2, live3;
+  LifeState dead0, dead1, dead2, dead4, dead5, dead6;
+
+  bool operator==(const LifeStable &o) const {
+    return state == o.state && unknown == o.unknown && live2 == o.live2 && live3 == o.live3 && dead0 == o.dead0 &&
+           dead1 == o.dead1 && dead2 == o.dead2 && dead4 == o.dead4 && dead5 == o.dead5 && dead6 == o.dead6;
+  }
+  // LifeStable.hpp:308-318: `cells` keep only the options in `options`, i.e.
+  // every other option's plane gets them
+  void RestrictOptions(const LifeState &cells, StableOptions options) {
+    LifeState *const plane[8] = {&live2, &live3, &dead0, &dead1, &dead2, &dead4, &dead5, &dead6};
+    for (int k = 0; k < 8; ++k)
+      if (!((unsigned char)options >> k & 1)) *plane[k] |= cells;
+  }
+  void SetOn(const LifeState &which) {  // LifeStable.hpp:320-329
+    state |= which;
+    unknown &= ~which;
+    RestrictOptions(which, StableOptions::LIVE);
+  }
+  void SetOff(const LifeState &which) {  // LifeStable.hpp:330-335
+    state &= ~which;
+    unknown &= ~which;
+    RestrictOptions(which, StableOptions::DEAD);
+  }
+};
+
+// LifeWeld.hpp:18-400 (the search subset): a state plus a frozen 3-bit
+// neighbour count added when stepping.  The batched forms are
+// lifeapi::Weld*Batch in lifeapi/batch.hpp.
 struct LifeWeld {
   LifeState state, frozen2, frozen1, frozen0;
 
@@ -752,15 +797,125 @@ struct LifeWeld {
       state[i] = (s0 ^ s2) & (s1 ^ s2) & (state[i] | s0);
     }
   }
-};
+  LifeWeld Stepped() const {
+    LifeWeld w = *this;
+    w.Step();
+    return w;
+  }
+  LifeState AllFrozen() const { return frozen2 | frozen1 | frozen0; }  // :40
+  LifeWeld operator|(const LifeWeld &o) const {                         // :42-45
+    return {state | o.state, frozen2 | o.frozen2, frozen1 | o.frozen1, frozen0 | o.frozen0};
+  }
+  LifeWeld Moved(std::pair<int, int> v) const {  // :65-68
+    return {state.Moved(v), frozen2.Moved(v), frozen1.Moved(v), frozen0.Moved(v)};
+  }
+  // the cells with no frozen count, and everything next to one
+  LifeState NonFrozenZOI() const { return (state & ~AllFrozen()).ZOI(); }
 
-// LifeStable.hpp:41-53: the ten planes of the stable-search state (options
-// stored as "1 = ruled out").  Propagation runs on the GPU:
-// lifeapi::PropagateStepBatch / PropagateBatch in lifeapi/batch.hpp.
-struct LifeStable {
-  LifeState state, unknown;
-  LifeState live2, live3;
-  LifeState dead0, dead1, dead2, dead4, dead5, dead6;
+  // LifeWeld.hpp:133-159: the part of `state` within reach of the cells that
+  // `required` does not cover; the stator dropped from it is remembered as a
+  // frozen count on the required cells next to the active region and on the
+  // cells where the kept part alone would see a birth.  (The stator's count
+  // has a bit 3; it is dropped, as in the reference.)
+  static LifeWeld FromRequired(const LifeState &state, const LifeState &required) {
+    const LifeState reach = (state.ZOI() & ~required).ZOI();
+    const LifeState stator = state & ~reach, kept = state & ~stator;
+    const LifeState frozen = (reach & required) | (kept.Stepped() & ~kept);
+    const NeighbourCount c(stator);
+    return {kept, c.bit2 & frozen, c.bit1 & frozen, c.bit0 & frozen};
+  }
+  // LifeWeld.hpp:188-191: what to match to know that it has recovered
+  LifeTarget ToTarget() const { return LifeTarget(state, NonFrozenZOI() & ~state); }
+
+  // LifeWeld.hpp:279-325
+  LifeStable ToStable() const {
+    LifeStable st;
+    st.unknown = ~LifeState();
+    const NeighbourCount sum = SumCounts();
+    const LifeState frozen = AllFrozen(), live = frozen & state, dead = frozen & ~state;
+    st.SetOn(state);
+    st.SetOff(~state & NonFrozenZOI());
+    using enum StableOptions;
+    st.RestrictOptions(live & sum.WithExactly(3), LIVE2);  // (the sum counts the centre)
+    st.RestrictOptions(live & sum.WithExactly(4), LIVE3);
+    st.RestrictOptions(dead & sum.WithExactly(1), DEAD1);
+    st.RestrictOptions(dead & sum.WithExactly(2), DEAD2);
+    st.RestrictOptions(dead & sum.WithExactly(4), DEAD4);
+    st.RestrictOptions(dead & sum.WithExactly(5), DEAD5);
+    st.RestrictOptions(dead & sum.WithExactly(6), DEAD6);
+    return st;
+  }
+  // LifeWeld.hpp:327-400.  The reference replays the reaction twice; every
+  // update is an OR into an option plane or an AND-NOT into unknown whose
+  // operand does not depend on the stable, so one replay does both.
+  LifeStable ToStable(const LifeState &active, unsigned duration, const LifeState &mask = ~LifeState()) const {
+    LifeStable st = ToStable();
+    const NeighbourCount mine(state);
+    LifeWeld current = *this;
+    current.state |= active;
+    LifeState everActive;
+    using enum StableOptions;
+    // {count of current.state, count of state, the one option that goes} of the cells that stay dead
+    static constexpr struct { unsigned now, mine; StableOptions gone; } kStay[11] = {
+        {1, 0, DEAD2}, {2, 0, DEAD1}, {2, 1, DEAD2}, {1, 2, DEAD4}, {0, 2, DEAD5}, {3, 4, DEAD4},
+        {2, 4, DEAD5}, {1, 4, DEAD6}, {3, 5, DEAD5}, {2, 5, DEAD6}, {3, 6, DEAD6}};
+    for (unsigned g = 0; g < duration; ++g) {
+      everActive |= state ^ current.state;
+      const LifeWeld next = current.Stepped();
+      const LifeState dead = mask & ~state & ~current.state;
+      const LifeState born = dead & next.state, stay = dead & ~next.state;
+      const NeighbourCount now(current.state);
+      st.RestrictOptions(born & now.WithExactly(3) & mine.WithExactly(0), DEAD0);
+      st.RestrictOptions(born & now.WithExactly(3) & mine.WithExactly(1), DEAD1);
+      st.RestrictOptions(born & now.WithExactly(3) & mine.WithExactly(2), DEAD2);
+      for (const auto &r : kStay) st.RestrictOptions(stay & now.WithExactly(r.now) & mine.WithExactly(r.mine), ~r.gone);
+      if (next == current) break;  // a fixed point: every later generation repeats this one
+      current = next;
+    }
+    st.SetOff(mask & ~state & everActive);
+    return st;
+  }
+
+  // LifeWeld.hpp:206-245: LifeState::InteractionOffsets with every plane but
+  // the overlap term's kept only inside its side's NonFrozenZOI() -- except
+  // that, as in the reference (:238-239), the second operand of each birth
+  // term is cut by the FIRST operand's region: other's dead2 plane by ours,
+  // our dead2 plane by other's.
+  LifeState InteractionOffsets(const LifeWeld &other) const {
+    struct Planes {
+      LifeState cells, dead1, dead2, live3, live4up, dead2up, dead1up;
+      explicit Planes(const LifeState &s) {
+        const NeighbourCount c(s);
+        const LifeState high = c.bit3 | c.bit2, low = ~high;
+        cells = s;
+        dead1 = low & ~c.bit1 & c.bit0 & ~s;
+        dead2 = low & c.bit1 & ~c.bit0 & ~s;
+        live3 = low & c.bit1 & c.bit0 & s;
+        live4up = high & s;
+        dead2up = (high | c.bit1) & ~s;
+        dead1up = (high | c.bit1 | c.bit0) & ~s;
+      }
+    };
+    const Planes a(state), b(other.state.Mirrored());
+    const LifeState ak = NonFrozenZOI(), bk = other.NonFrozenZOI().Mirrored();
+    return a.cells.Convolve(b.cells) | (a.dead1 & ak).Convolve(b.dead2 & ak) | (b.dead1 & bk).Convolve(a.dead2 & bk) |
+           (a.live3 & ak).Convolve(b.dead2up & bk) | (a.live4up & ak).Convolve(b.dead1up & bk) |
+           (b.live3 & bk).Convolve(a.dead2up & ak) | (b.live4up & bk).Convolve(a.dead1up & ak);
+  }
+
+ private:
+  // the inclusive count of state plus the frozen number, four bits (:295-299)
+  NeighbourCount SumCounts() const {
+    NeighbourCount c(state), sum;
+    for (int i = 0; i < N; ++i) {
+      uint64_t k0, k1, k2;
+      LifeState::HalfAdd(sum.bit0[i], k0, c.bit0[i], frozen0[i]);
+      LifeState::FullAdd(sum.bit1[i], k1, c.bit1[i], frozen1[i], k0);
+      LifeState::FullAdd(sum.bit2[i], k2, c.bit2[i], frozen2[i], k1);
+      sum.bit3[i] = c.bit3[i] ^ k2;
+    }
+    return sum;
+  }
 };
 
 }  // namespace lifeapi

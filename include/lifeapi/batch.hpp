@@ -401,6 +401,90 @@ std::vector<std::vector<S>> Components(std::span<const S> states, const C &coron
   return detail::components(states, words(&corona), device);
 }
 
+// ---- making LifeWelds and what a search derives from them ----
+//
+// welds[i] = LifeWeld::FromRequired(states[i], required)  (LifeWeld.hpp:133-159)
+template <LifeWeldLayout W, LifeStateLayout S>
+std::vector<W> WeldFromRequiredBatch(std::span<const S> states, const S &required, int device = 0) {
+  std::vector<W> welds(states.size());
+  check(lifeapi_weld_from_required_batch(words(states.data()), words(&required), 0, words(welds.data()),
+                                         states.size(), device));
+  return welds;
+}
+// ... with required[i] for states[i]
+template <LifeWeldLayout W, LifeStateLayout S>
+std::vector<W> WeldFromRequiredBatch(std::span<const S> states, std::span<const S> required, int device = 0) {
+  if (required.size() != states.size()) throw Error(LIFEAPI_E_INVALID, "lifeapi: size mismatch");
+  std::vector<W> welds(states.size());
+  check(lifeapi_weld_from_required_batch(words(states.data()), words(required.data()), 1, words(welds.data()),
+                                         states.size(), device));
+  return welds;
+}
+
+// targets[i] = welds[i].ToTarget()  (LifeWeld.hpp:188-191)
+template <LifeTargetLayout T, LifeWeldLayout W>
+std::vector<T> WeldToTargetBatch(std::span<const W> welds, int device = 0) {
+  const size_t n = welds.size();
+  std::vector<uint64_t> wanted(n * 64), unwanted(n * 64);
+  check(lifeapi_weld_to_target_batch(words(welds.data()), wanted.data(), unwanted.data(), n, device));
+  std::vector<T> targets(n);
+  for (size_t i = 0; i < n; ++i) {
+    uint64_t *t = words(&targets[i]);
+    std::copy_n(wanted.data() + i * 64, 64, t);
+    std::copy_n(unwanted.data() + i * 64, 64, t + 64);
+  }
+  return targets;
+}
+
+namespace detail {
+template <LifeStableLayout B, LifeWeldLayout W>
+std::vector<B> weld_to_stable(std::span<const W> welds, const uint64_t *active, int per, const uint64_t *mask,
+                              unsigned duration, int device) {
+  std::vector<B> stables(welds.size());
+  check(lifeapi_weld_to_stable_batch(words(welds.data()), active, per, mask, duration, words(stables.data()),
+                                     welds.size(), device));
+  return stables;
+}
+}  // namespace detail
+
+// stables[i] = welds[i].ToStable()  (LifeWeld.hpp:279-325), ready for PropagateBatch
+template <LifeStableLayout B, LifeWeldLayout W>
+std::vector<B> WeldToStableBatch(std::span<const W> welds, int device = 0) {
+  return detail::weld_to_stable<B>(welds, nullptr, 0, nullptr, 0, device);
+}
+// stables[i] = welds[i].ToStable(active, duration[, mask])  (LifeWeld.hpp:327-400)
+template <LifeStableLayout B, LifeWeldLayout W, LifeStateLayout S>
+std::vector<B> WeldToStableBatch(std::span<const W> welds, const S &active, unsigned duration, int device = 0) {
+  return detail::weld_to_stable<B>(welds, words(&active), 0, nullptr, duration, device);
+}
+template <LifeStableLayout B, LifeWeldLayout W, LifeStateLayout S>
+std::vector<B> WeldToStableBatch(std::span<const W> welds, const S &active, unsigned duration, const S &mask,
+                                 int device = 0) {
+  return detail::weld_to_stable<B>(welds, words(&active), 0, words(&mask), duration, device);
+}
+// ... with active[i] for welds[i]
+template <LifeStableLayout B, LifeWeldLayout W, LifeStateLayout S>
+std::vector<B> WeldToStableBatch(std::span<const W> welds, std::span<const S> active, unsigned duration,
+                                 int device = 0) {
+  if (active.size() != welds.size()) throw Error(LIFEAPI_E_INVALID, "lifeapi: size mismatch");
+  return detail::weld_to_stable<B>(welds, words(active.data()), 1, nullptr, duration, device);
+}
+template <LifeStableLayout B, LifeWeldLayout W, LifeStateLayout S>
+std::vector<B> WeldToStableBatch(std::span<const W> welds, std::span<const S> active, unsigned duration,
+                                 const S &mask, int device = 0) {
+  if (active.size() != welds.size()) throw Error(LIFEAPI_E_INVALID, "lifeapi: size mismatch");
+  return detail::weld_to_stable<B>(welds, words(active.data()), 1, words(&mask), duration, device);
+}
+
+// out[i] = welds[i].InteractionOffsets(other)  (LifeWeld.hpp:206-245)
+template <LifeStateLayout S, LifeWeldLayout W>
+std::vector<S> WeldInteractionOffsetsBatch(std::span<const W> welds, const W &other, int device = 0) {
+  std::vector<S> out(welds.size());
+  check(lifeapi_weld_interaction_offsets_batch(words(welds.data()), words(&other), words(out.data()), welds.size(),
+                                               device));
+  return out;
+}
+
 // The search-loop idiom over a batch, in place (LifeAPI.hpp:1196-1216,
 // LifeTarget.hpp:44-51):
 //     for (unsigned g = 1; g <= gens; ++g) { s.Step(); if (!first && s.Contains(target)) first = g; }

@@ -36,6 +36,15 @@
  *                                LifeState::ComponentContaining
  *                                                           LifeAPI.hpp:655-665, 1184-1188
  *   lifeapi_components_batch[_dev] LifeState::Components    LifeAPI.hpp:667-676, 1189-1193
+ *   lifeapi_weld_from_required_batch[_dev]
+ *                                LifeWeld::FromRequired     LifeWeld.hpp:133-159
+ *   lifeapi_weld_to_target_batch[_dev] LifeWeld::ToTarget   LifeWeld.hpp:188-191
+ *   lifeapi_weld_to_stable_batch[_dev] LifeWeld::ToStable() LifeWeld.hpp:279-325
+ *                                LifeWeld::ToStable(active, duration, mask)
+ *                                                           LifeWeld.hpp:327-400
+ *   lifeapi_weld_interaction_offsets_batch[_dev]
+ *                                LifeWeld::InteractionOffsets(const LifeWeld &)
+ *                                                           LifeWeld.hpp:206-245
  *   lifeapi_fill_random_dev      LifeState::RandomState()   LifeAPI.hpp:63-69
  *                                (seeded splitmix64; mode 1 = RandomState's
  *                                 [2^61, 2^62) column distribution)
@@ -241,6 +250,39 @@ int lifeapi_stable_vulnerable_batch_dev(const uint64_t *d_planes, uint64_t *d_ou
  * LifeWeld[n] = {state, frozen2, frozen1, frozen0} x 64 words (the struct's
  * member order, LifeWeld.hpp:18-20); only the state planes change.        */
 int lifeapi_weld_step_batch_dev(uint64_t *d_welds, size_t n, uint32_t generations, void *stream);
+/* The LifeWeld construction family.  LifeWeld[n] and LifeStable[n] in the
+ * layouts above; every function is defined for any bit patterns (frozen counts
+ * on live cells, a `required` unrelated to the state, an `active` over the
+ * state).  No output may overlap an input or another output.
+ *
+ * d_welds[u] = LifeWeld::FromRequired(d_states[u], required_u) (LifeWeld.hpp:
+ * 133-159).  d_required: 64 words (per_universe_required == 0) or n x 64.   */
+int lifeapi_weld_from_required_batch_dev(const uint64_t *d_states, const uint64_t *d_required,
+                                         int per_universe_required, uint64_t *d_welds, size_t n,
+                                         void *stream);
+/* (d_wanted[u], d_unwanted[u]) = d_welds[u].ToTarget() (LifeWeld.hpp:188-191),
+ * the halves of a LifeTarget, n x 64 words each.                            */
+int lifeapi_weld_to_target_batch_dev(const uint64_t *d_welds, uint64_t *d_wanted, uint64_t *d_unwanted,
+                                     size_t n, void *stream);
+/* d_stables[u] = d_welds[u].ToStable(active_u, duration, mask) (LifeWeld.hpp:
+ * 279-400), ready for lifeapi_stable_pass_batch_dev.
+ * d_active: NULL (the empty state), 64 words (per_universe_active == 0) or
+ *   n x 64.  d_mask: NULL (= ~LifeState(), the reference's default) or 64 words.
+ * duration == 0 is exactly ToStable() (LifeWeld.hpp:279-325), whatever active
+ * and mask are.  duration > 65536 is LIFEAPI_E_INVALID (a bound on one
+ * launch's time, which grows in proportion to duration; a reaction that
+ * reaches a fixed point stops costing there).                               */
+int lifeapi_weld_to_stable_batch_dev(const uint64_t *d_welds, const uint64_t *d_active,
+                                     int per_universe_active, const uint64_t *d_mask, uint32_t duration,
+                                     uint64_t *d_stables, size_t n, void *stream);
+/* d_out[u] = d_welds[u].InteractionOffsets(other) (LifeWeld.hpp:206-245):
+ * LifeState::InteractionOffsets with every plane but the overlap term's
+ * masked by its side's (state & ~frozen2 & ~frozen1 & ~frozen0).ZOI() -- except
+ * that, as in the reference (LifeWeld.hpp:238-239), the second operand of
+ * each birth term is masked by the FIRST operand's side.
+ * d_other: one LifeWeld, 256 words.                                         */
+int lifeapi_weld_interaction_offsets_batch_dev(const uint64_t *d_welds, const uint64_t *d_other,
+                                               uint64_t *d_out, size_t n, void *stream);
 /* Config-5 ternary step: bitslicing/unknown_step_refined.hpp:1-85 applied
  * per column with s2..s0 / on2..on0 = bits 2..0 of NeighbourCount
  * (NeighbourCount.hpp:40-70) of stable.state / current.state.
@@ -320,6 +362,17 @@ int lifeapi_component_containing_batch(const uint64_t *states, const uint64_t *s
                                        size_t n, int device);
 int lifeapi_components_batch(const uint64_t *states, const uint64_t *corona, uint32_t *count,
                              uint64_t *components, uint32_t max_components, size_t n, int device);
+/* host forms of the LifeWeld construction entry points: the same arguments
+ * and the same overlap rules, on host arrays                                */
+int lifeapi_weld_from_required_batch(const uint64_t *states, const uint64_t *required,
+                                     int per_universe_required, uint64_t *welds, size_t n, int device);
+int lifeapi_weld_to_target_batch(const uint64_t *welds, uint64_t *wanted, uint64_t *unwanted, size_t n,
+                                 int device);
+int lifeapi_weld_to_stable_batch(const uint64_t *welds, const uint64_t *active, int per_universe_active,
+                                 const uint64_t *mask, uint32_t duration, uint64_t *stables, size_t n,
+                                 int device);
+int lifeapi_weld_interaction_offsets_batch(const uint64_t *welds, const uint64_t *other, uint64_t *out,
+                                           size_t n, int device);
 /* host form of lifeapi_step_contains_batch_dev: the search-loop idiom
  * "for g in 1..gens: s.Step(); if (s.Contains(target)) ..." (LifeAPI.hpp:
  * 1196-1216, LifeTarget.hpp:44-51) over n host universes; final (may be NULL,

@@ -745,6 +745,73 @@ int lifeapi_components_batch(const uint64_t *states, const uint64_t *corona, uin
                     });
 }
 
+// the LifeWeld construction family: the argument checks that need no device
+// are the *_dev call's own, made on the host pointers before anything is staged
+int lifeapi_weld_from_required_batch(const uint64_t *states, const uint64_t *required, int per_universe_required,
+                                     uint64_t *welds, size_t n, int device) {
+  if (n == 0) return LIFEAPI_OK;
+  if (!states || !required || !welds || !aligned8(states) || !aligned8(required) || !aligned8(welds))
+    return fail(LIFEAPI_E_INVALID, "null or misaligned pointer to lifeapi_weld_from_required_batch%s");
+  const bool per = per_universe_required != 0;
+  if (ranges_overlap(welds, n * 2048, states, n * 512) || ranges_overlap(welds, n * 2048, required, per ? n * 512 : 512))
+    return fail(LIFEAPI_E_INVALID, "lifeapi_weld_from_required_batch: welds overlaps an input%s");
+  return host_batch(n, device, {{states, nullptr, 512}, {required, nullptr, 512, !per}, {nullptr, welds, 2048}},
+                    [=](void *const *d, size_t m, hipStream_t s) {
+                      return lifeapi_weld_from_required_batch_dev((const uint64_t *)d[0], (const uint64_t *)d[1], per,
+                                                                  (uint64_t *)d[2], m, s);
+                    });
+}
+
+int lifeapi_weld_to_target_batch(const uint64_t *welds, uint64_t *wanted, uint64_t *unwanted, size_t n, int device) {
+  if (n == 0) return LIFEAPI_OK;
+  if (!welds || !wanted || !unwanted || !aligned8(welds) || !aligned8(wanted) || !aligned8(unwanted))
+    return fail(LIFEAPI_E_INVALID, "null or misaligned pointer to lifeapi_weld_to_target_batch%s");
+  if (ranges_overlap(wanted, n * 512, welds, n * 2048) || ranges_overlap(unwanted, n * 512, welds, n * 2048) ||
+      ranges_overlap(wanted, n * 512, unwanted, n * 512))
+    return fail(LIFEAPI_E_INVALID, "lifeapi_weld_to_target_batch: an output overlaps the welds or the other output%s");
+  return host_batch(n, device, {{welds, nullptr, 2048}, {nullptr, wanted, 512}, {nullptr, unwanted, 512}},
+                    [](void *const *d, size_t m, hipStream_t s) {
+                      return lifeapi_weld_to_target_batch_dev((const uint64_t *)d[0], (uint64_t *)d[1],
+                                                              (uint64_t *)d[2], m, s);
+                    });
+}
+
+int lifeapi_weld_to_stable_batch(const uint64_t *welds, const uint64_t *active, int per_universe_active,
+                                 const uint64_t *mask, uint32_t duration, uint64_t *stables, size_t n, int device) {
+  const int rc = lifeapi_weld_to_stable_batch_dev(nullptr, nullptr, 0, nullptr, duration, nullptr, 0, nullptr);
+  if (rc != LIFEAPI_OK || n == 0) return rc;
+  if (!welds || !stables || !aligned8(welds) || !aligned8(stables) || !aligned8(active) || !aligned8(mask))
+    return fail(LIFEAPI_E_INVALID, "null or misaligned pointer to lifeapi_weld_to_stable_batch%s");
+  const bool act = active != nullptr, per = act && per_universe_active != 0, msk = mask != nullptr;
+  if (ranges_overlap(stables, n * 5120, welds, n * 2048) ||
+      (act && ranges_overlap(stables, n * 5120, active, per ? n * 512 : 512)) ||
+      (msk && ranges_overlap(stables, n * 5120, mask, 512)))
+    return fail(LIFEAPI_E_INVALID, "lifeapi_weld_to_stable_batch: stables overlaps an input%s");
+  // (an input the caller leaves out keeps a one-byte slot and is not copied)
+  return host_batch(n, device,
+                    {{welds, nullptr, 2048}, {nullptr, stables, 5120}, {active, nullptr, act ? size_t(512) : size_t(1), act && !per},
+                     {mask, nullptr, msk ? size_t(512) : size_t(1), msk}},
+                    [=](void *const *d, size_t m, hipStream_t s) {
+                      return lifeapi_weld_to_stable_batch_dev((const uint64_t *)d[0], act ? (const uint64_t *)d[2] : nullptr,
+                                                              per, msk ? (const uint64_t *)d[3] : nullptr, duration,
+                                                              (uint64_t *)d[1], m, s);
+                    });
+}
+
+int lifeapi_weld_interaction_offsets_batch(const uint64_t *welds, const uint64_t *other, uint64_t *out, size_t n,
+                                           int device) {
+  if (n == 0) return LIFEAPI_OK;
+  if (!welds || !other || !out || !aligned8(welds) || !aligned8(other) || !aligned8(out))
+    return fail(LIFEAPI_E_INVALID, "null or misaligned pointer to lifeapi_weld_interaction_offsets_batch%s");
+  if (ranges_overlap(out, n * 512, welds, n * 2048) || ranges_overlap(out, n * 512, other, 2048))
+    return fail(LIFEAPI_E_INVALID, "lifeapi_weld_interaction_offsets_batch: out overlaps an input%s");
+  return host_batch(n, device, {{welds, nullptr, 2048}, {nullptr, out, 512}, {other, nullptr, 2048, true}},
+                    [](void *const *d, size_t m, hipStream_t s) {
+                      return lifeapi_weld_interaction_offsets_batch_dev((const uint64_t *)d[0], (const uint64_t *)d[2],
+                                                                        (uint64_t *)d[1], m, s);
+                    });
+}
+
 int lifeapi_step_contains_batch(const uint64_t *in, uint64_t *final_states, const uint64_t *wanted,
                                 const uint64_t *unwanted, uint32_t *first_gen, size_t n,
                                 uint32_t generations, int device) {

@@ -91,6 +91,14 @@ _SIGS = {
     "lifeapi_first_on_batch": ([_vp, _vp, _sz, _int], _int),
     "lifeapi_component_containing_batch": ([_vp, _vp, _int, _vp, _vp, _sz, _int], _int),
     "lifeapi_components_batch": ([_vp, _vp, _vp, _vp, _u32, _sz, _int], _int),
+    "lifeapi_weld_from_required_batch_dev": ([_vp, _vp, _int, _vp, _sz, _vp], _int),
+    "lifeapi_weld_to_target_batch_dev": ([_vp, _vp, _vp, _sz, _vp], _int),
+    "lifeapi_weld_to_stable_batch_dev": ([_vp, _vp, _int, _vp, _u32, _vp, _sz, _vp], _int),
+    "lifeapi_weld_interaction_offsets_batch_dev": ([_vp, _vp, _vp, _sz, _vp], _int),
+    "lifeapi_weld_from_required_batch": ([_vp, _vp, _int, _vp, _sz, _int], _int),
+    "lifeapi_weld_to_target_batch": ([_vp, _vp, _vp, _sz, _int], _int),
+    "lifeapi_weld_to_stable_batch": ([_vp, _vp, _int, _vp, _u32, _vp, _sz, _int], _int),
+    "lifeapi_weld_interaction_offsets_batch": ([_vp, _vp, _vp, _sz, _int], _int),
 }
 for _name, (_args, _res) in _SIGS.items():
     _f = getattr(lib, _name)
@@ -591,6 +599,133 @@ def weld_step(welds: torch.Tensor, generations: int = 1, stream=None) -> torch.T
     _check(lib.lifeapi_weld_step_batch_dev(welds.data_ptr(), _planes(welds, 4, "welds"), generations,
                                            _stream(stream)))
     return welds
+
+
+def _one_or_n(t: torch.Tensor, n: int, name: str) -> int:
+    """1 if t holds one universe per object of the batch, 0 if one for all"""
+    k = _universes(t, name)
+    if k != 1 and k != n:
+        raise ValueError(f"{name} must hold one universe or one per object")
+    return int(k == n and n != 1)
+
+
+def _out_planes(out: torch.Tensor | None, n: int, k: int, like: torch.Tensor, name: str) -> torch.Tensor:
+    if out is None:
+        return torch.empty((n, k * N), dtype=torch.int64, device=like.device)
+    if _planes(out, k, name) != n:
+        raise ValueError(f"{name} has a different number of objects")
+    return out
+
+
+def weld_from_required(states: torch.Tensor, required: torch.Tensor, out: torch.Tensor | None = None,
+                       stream=None) -> torch.Tensor:
+    """Per-universe ``LifeWeld::FromRequired(state, required)`` (LifeWeld.hpp:
+    133-159): (n, 4*64) {state, frozen2, frozen1, frozen0}.  ``required`` holds
+    one universe for the whole batch or one per universe."""
+    n = _universes(states)
+    per = _one_or_n(required, n, "required")
+    out = _out_planes(out, n, 4, states, "out")
+    _check(lib.lifeapi_weld_from_required_batch_dev(states.data_ptr(), required.data_ptr(), per, out.data_ptr(), n,
+                                                    _stream(stream)))
+    return out
+
+
+def weld_to_target(welds: torch.Tensor, wanted: torch.Tensor | None = None, unwanted: torch.Tensor | None = None,
+                   stream=None) -> tuple[torch.Tensor, torch.Tensor]:
+    """Per-weld ``ToTarget()`` (LifeWeld.hpp:188-191): (wanted, unwanted), (n, 64) each."""
+    n = _planes(welds, 4, "welds")
+    wanted = _out_planes(wanted, n, 1, welds, "wanted")
+    unwanted = _out_planes(unwanted, n, 1, welds, "unwanted")
+    _check(lib.lifeapi_weld_to_target_batch_dev(welds.data_ptr(), wanted.data_ptr(), unwanted.data_ptr(), n,
+                                                _stream(stream)))
+    return wanted, unwanted
+
+
+def weld_to_stable(welds: torch.Tensor, active: torch.Tensor | None = None, duration: int = 0,
+                   mask: torch.Tensor | None = None, out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+    """Per-weld ``ToStable(active, duration, mask)`` (LifeWeld.hpp:279-400) as
+    (n, 10*64) LifeStable planes, the layout :func:`stable_pass` takes.
+    ``active``: None (empty), one universe or one per weld; ``mask``: None (all
+    cells, the reference's default) or one universe.  ``duration == 0`` is
+    ``ToStable()``."""
+    n = _planes(welds, 4, "welds")
+    per = 0 if active is None else _one_or_n(active, n, "active")
+    if mask is not None and _universes(mask, "mask") != 1:
+        raise ValueError("mask must hold one universe")
+    out = _out_planes(out, n, 10, welds, "out")
+    _check(lib.lifeapi_weld_to_stable_batch_dev(welds.data_ptr(), None if active is None else active.data_ptr(), per,
+                                                None if mask is None else mask.data_ptr(), duration, out.data_ptr(),
+                                                n, _stream(stream)))
+    return out
+
+
+def weld_interaction_offsets(welds: torch.Tensor, other: torch.Tensor, out: torch.Tensor | None = None,
+                             stream=None) -> torch.Tensor:
+    """Per-weld ``InteractionOffsets(other)`` (LifeWeld.hpp:206-245), ``other`` one
+    LifeWeld of 4*64 words: (n, 64)."""
+    n = _planes(welds, 4, "welds")
+    if _planes(other, 4, "other") != 1:
+        raise ValueError("other must hold one LifeWeld (4*64 words)")
+    out = _out_planes(out, n, 1, welds, "out")
+    _check(lib.lifeapi_weld_interaction_offsets_batch_dev(welds.data_ptr(), other.data_ptr(), out.data_ptr(), n,
+                                                          _stream(stream)))
+    return out
+
+
+def _host_planes(a: np.ndarray, k: int, name: str) -> tuple[np.ndarray, int]:
+    a = np.ascontiguousarray(a, dtype=np.uint64)
+    if a.size % (k * N):
+        raise ValueError(f"{name} must hold whole objects of {k}*64 words")
+    return a, a.size // (k * N)
+
+
+def weld_from_required_host(states: np.ndarray, required: np.ndarray, device: int = 0) -> np.ndarray:
+    """Host-pointer ``lifeapi_weld_from_required_batch``."""
+    src, req = _host_u64(states), _host_u64(required)
+    n, k = src.size // N, req.size // N
+    if k != 1 and k != n:
+        raise ValueError("required must hold one universe or one per universe")
+    out = np.empty((n, 4 * N), dtype=np.uint64)
+    _check(lib.lifeapi_weld_from_required_batch(src.ctypes.data, req.ctypes.data, int(k == n and n != 1),
+                                                out.ctypes.data, n, device))
+    return out
+
+
+def weld_to_target_host(welds: np.ndarray, device: int = 0) -> tuple[np.ndarray, np.ndarray]:
+    """Host-pointer ``lifeapi_weld_to_target_batch``."""
+    src, n = _host_planes(welds, 4, "welds")
+    wanted, unwanted = np.empty((n, N), dtype=np.uint64), np.empty((n, N), dtype=np.uint64)
+    _check(lib.lifeapi_weld_to_target_batch(src.ctypes.data, wanted.ctypes.data, unwanted.ctypes.data, n, device))
+    return wanted, unwanted
+
+
+def weld_to_stable_host(welds: np.ndarray, active: np.ndarray | None = None, duration: int = 0,
+                        mask: np.ndarray | None = None, device: int = 0) -> np.ndarray:
+    """Host-pointer ``lifeapi_weld_to_stable_batch``."""
+    src, n = _host_planes(welds, 4, "welds")
+    act = None if active is None else _host_u64(active)
+    msk = None if mask is None else _host_u64(mask)
+    if act is not None and act.size // N not in (1, n):
+        raise ValueError("active must hold one universe or one per weld")
+    if msk is not None and msk.size != N:
+        raise ValueError("mask must hold one universe")
+    out = np.empty((n, 10 * N), dtype=np.uint64)
+    _check(lib.lifeapi_weld_to_stable_batch(src.ctypes.data, None if act is None else act.ctypes.data,
+                                            int(act is not None and act.size // N == n and n != 1),
+                                            None if msk is None else msk.ctypes.data, duration, out.ctypes.data, n,
+                                            device))
+    return out
+
+
+def weld_interaction_offsets_host(welds: np.ndarray, other: np.ndarray, device: int = 0) -> np.ndarray:
+    """Host-pointer ``lifeapi_weld_interaction_offsets_batch``."""
+    src, n = _host_planes(welds, 4, "welds")
+    oth, k = _host_planes(other, 4, "other")
+    if k != 1:
+        raise ValueError("other must hold one LifeWeld (4*64 words)")
+    out = np.empty((n, N), dtype=np.uint64)
+    _check(lib.lifeapi_weld_interaction_offsets_batch(src.ctypes.data, oth.ctypes.data, out.ctypes.data, n, device))
+    return out
 
 
 STABLE_PASSES = ("sync", "options", "signal", "step", "propagate", "stabilise")
