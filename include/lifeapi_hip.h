@@ -236,10 +236,18 @@ int lifeapi_interaction_counts_batch_dev(const uint64_t *d_in, uint64_t *d_out, 
  * pass: 0 SynchroniseStateKnown (LifeStable.hpp:526-556), 1 UpdateOptions
  * (:558-615), 2 SignalNeighbours (:617-675), 3 PropagateStep (:695-716),
  * 4 Propagate (:718-729, at most max_iters steps; 0 = 2^20),
- * 5 StabiliseOptions (:677-693, the same bound).
- * d_flags[u] = consistent | changed << 1 (| 4 if max_iters stopped 4 / 5),
- * i.e. the PropagateResult; planes are left exactly as the reference leaves
- * them, including on an inconsistent early return.  Only the 128-byte lines
+ * 5 StabiliseOptions (:677-693, the same bound); passes 0-3 ignore max_iters.
+ * d_flags[u] = consistent | changed << 1, i.e. the PropagateResult; planes
+ * are left exactly as the reference leaves them, including on an
+ * inconsistent early return.  Where max_iters stopped 4 / 5 -- max_iters
+ * iterations ran, none inconsistent, and the last one still changed
+ * something -- d_flags[u] = 1 | 2 | 4 and the planes are the reference's
+ * after exactly max_iters iterations.  That includes an object whose
+ * max_iters-th iteration was the last to change anything: its planes are
+ * the fixpoint's already, but the iteration that would confirm it has not
+ * run; from max_iters + 1 on its flags are 1 | 2.  An iteration found
+ * inconsistent within the bound gives 0, one that changes nothing 1 | 2 (or 1
+ * if it was the first), whatever the bound.  Only the 128-byte lines
  * holding a changed column are written back (the rest is already there).  */
 int lifeapi_stable_pass_batch_dev(uint64_t *d_planes, uint8_t *d_flags, size_t n, int pass,
                                   uint32_t max_iters, void *stream);

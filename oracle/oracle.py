@@ -167,6 +167,59 @@ class Port:
                                                    self._stt[1].ctypes.data_as(u8))
         return out, flags
 
+    def stable_iteration(self, planes: np.ndarray, which: int):
+        """One iteration of Propagate (`which` 4: pass 3, a PropagateStep) or of
+        StabiliseOptions (5: pass 0, then pass 1 unless pass 0 was
+        inconsistent) on (n, 640) planes, composed from stable_pass; returns
+        (planes, flags), flags 0 (inconsistent, the planes as the partial
+        iteration left them), 1 (nothing changed) or 3."""
+        assert which in (4, 5), which
+        if which == 4:
+            out, fl = self.stable_pass(planes, 3)
+        else:
+            out, fl = self.stable_pass(planes, 0)
+            ok = (fl & 1) != 0
+            if ok.any():
+                out[ok], f1 = self.stable_pass(out[ok], 1)
+                fl[ok] = (f1 & 1) | ((fl[ok] | f1) & 2)
+        fl[(fl & 1) == 0] = 0
+        return out, fl
+
+    def stable_pass_bounded(self, planes: np.ndarray, which: int, max_iters: int = 0):
+        """Propagate (`which` 4) or StabiliseOptions (5) stopped after at most
+        `max_iters` iterations (0: 2^20) on (n, 640) planes, as
+        lifeapi_stable_pass_batch_dev bounds them; returns (planes, flags).
+        Per object, iteration after iteration (stable_iteration):
+          * an inconsistent iteration ends it with flag 0, the planes as that
+            partial iteration left them;
+          * an iteration that changes nothing ends it with flag
+            1 | 2 * (an earlier iteration changed);
+          * when `max_iters` iterations have run and the last of them changed
+            something, the flag is 1 | 2 | 4 and the planes are those after
+            `max_iters` iterations.
+        The boundary: an object whose s-th iteration is the last one that
+        changes anything holds its fixpoint's planes after max_iters = s
+        already, but the iteration that would confirm it (the s + 1-th,
+        changing nothing) has not run, so the flag there is 7, not 3; from
+        max_iters = s + 1 on it is 3.  With max_iters = 0 this is
+        stable_pass(planes, which)."""
+        out = np.ascontiguousarray(planes, dtype=np.uint64).reshape(-1, 640).copy()
+        flags = np.zeros(out.shape[0], np.uint8)
+        ever = np.zeros(out.shape[0], np.uint8)
+        live = np.arange(out.shape[0])
+        limit = int(max_iters) if max_iters else 1 << 20
+        it = 0
+        while live.size and it < limit:
+            out[live], fl = self.stable_iteration(out[live], which)
+            still = fl == 1
+            flags[live[fl == 0]] = 0
+            flags[live[still]] = 1 | ever[live[still]]
+            live = live[fl == 3]
+            ever[live] = 2
+            it += 1
+        flags[live] = 1 | 2 | 4
+        return out, flags
+
     def stable_vulnerable(self, planes: np.ndarray) -> np.ndarray:
         """LifeStable::Vulnerable() (LifeStable.hpp:366-412) of (n, 640) planes."""
         if not hasattr(self, "_vtt"):
