@@ -122,6 +122,47 @@ std::vector<PropagateResult> StabiliseOptionsBatch(std::span<S> s, int device = 
   return detail::stable_pass(s, 5, 0, device);
 }
 
+namespace detail {
+inline std::vector<PropagateResult> results(const std::vector<uint8_t> &f) {
+  std::vector<PropagateResult> r(f.size());
+  for (size_t i = 0; i < f.size(); ++i) r[i] = {(f[i] & 1) != 0, (f[i] & 2) != 0};
+  return r;
+}
+}  // namespace detail
+
+// s[i].PropagateStrip(columns[i]) (LifeStable.hpp:1238-1249), in place: the
+// propagation TestUnknown runs, which stops at the strip's edge
+template <LifeStableLayout S>
+std::vector<PropagateResult> PropagateStripBatch(std::span<S> s, std::span<const uint8_t> columns, int device = 0) {
+  if (columns.size() != s.size()) throw Error(LIFEAPI_E_INVALID, "lifeapi: size mismatch");
+  std::vector<uint8_t> f(s.size());
+  check(lifeapi_stable_strip_pass_batch(words(s.data()), columns.data(), f.data(), s.size(), 4, 0, device));
+  return detail::results(f);
+}
+// s[i].TestUnknowns(cells) (LifeStable.hpp:1321-1338; TestUnknown :1251-1284,
+// Join :217-233), in place: one mask for the batch, or one per object
+template <LifeStableLayout S, LifeStateLayout L>
+std::vector<PropagateResult> TestUnknownsBatch(std::span<S> s, const L &cells, int device = 0) {
+  std::vector<uint8_t> f(s.size());
+  check(lifeapi_stable_test_unknowns_batch(words(s.data()), words(&cells), 0, f.data(), s.size(), 0, device));
+  return detail::results(f);
+}
+template <LifeStableLayout S, LifeStateLayout L>
+std::vector<PropagateResult> TestUnknownsBatch(std::span<S> s, std::span<const L> cells, int device = 0) {
+  if (cells.size() != s.size()) throw Error(LIFEAPI_E_INVALID, "lifeapi: size mismatch");
+  std::vector<uint8_t> f(s.size());
+  check(lifeapi_stable_test_unknowns_batch(words(s.data()), words(cells.data()), 1, f.data(), s.size(), 0, device));
+  return detail::results(f);
+}
+// s[i].PropagateAndTest() (LifeStable.hpp:163-184), in place: a search node's
+// Propagate / TestUnknowns(Vulnerable().ZOI()) rounds to their fixed point
+template <LifeStableLayout S>
+std::vector<PropagateResult> PropagateAndTestBatch(std::span<S> s, int device = 0) {
+  std::vector<uint8_t> f(s.size());
+  check(lifeapi_stable_propagate_and_test_batch(words(s.data()), f.data(), s.size(), 0, device));
+  return detail::results(f);
+}
+
 // out[i] = s[i].Vulnerable()  (LifeStable.hpp:366-412)
 template <LifeStableLayout S, LifeStateLayout L>
 void VulnerableBatch(std::span<const S> s, std::span<L> out, int device = 0) {

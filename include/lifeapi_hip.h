@@ -45,6 +45,13 @@
  *   lifeapi_weld_interaction_offsets_batch[_dev]
  *                                LifeWeld::InteractionOffsets(const LifeWeld &)
  *                                                           LifeWeld.hpp:206-245
+ *   lifeapi_stable_strip_pass_batch[_dev]
+ *                                LifeStable::*Strip passes  LifeStable.hpp:921-948, 995-1249
+ *   lifeapi_stable_test_unknowns_batch[_dev]
+ *                                LifeStable::TestUnknowns   LifeStable.hpp:1321-1338
+ *                                (TestUnknown LifeStable.hpp:1251-1284, Join LifeStable.hpp:217-233)
+ *   lifeapi_stable_propagate_and_test_batch[_dev]
+ *                                LifeStable::PropagateAndTest LifeStable.hpp:163-184
  *   lifeapi_fill_random_dev      LifeState::RandomState()   LifeAPI.hpp:63-69
  *                                (seeded splitmix64; mode 1 = RandomState's
  *                                 [2^61, 2^62) column distribution)
@@ -254,6 +261,58 @@ int lifeapi_stable_pass_batch_dev(uint64_t *d_planes, uint8_t *d_flags, size_t n
 /* LifeStable::Vulnerable() (LifeStable.hpp:366-412) of every LifeStable[n]
  * (layout as above): d_out = n LifeStates.                                */
 int lifeapi_stable_vulnerable_batch_dev(const uint64_t *d_planes, uint64_t *d_out, size_t n, void *stream);
+/* The LifeStable lookahead family: one-cell lookahead and the strip passes it
+ * is built from, in place on LifeStable[n] (layout of
+ * lifeapi_stable_pass_batch_dev).  Every argument is checked before a device
+ * is touched: null or misaligned d_planes / d_cells, null d_columns / d_flags,
+ * d_cells, d_columns or d_flags overlapping d_planes and a pass outside 0..5
+ * are LIFEAPI_E_INVALID; n == 0 succeeds with any pointers.
+ *
+ * Strip passes, each object at its own column d_columns[u] (0..63; the low six
+ * bits are taken).
+ * pass: 0 SynchroniseStateKnownStrip (LifeStable.hpp:921-948)
+ *       1 UpdateOptionsStrip         (:1111-1195)
+ *       2 SignalNeighboursStrip      (:995-1109)
+ *       3 PropagateStepStrip         (:1215-1236)
+ *       4 PropagateStrip             (:1238-1249)
+ *       5 StabiliseOptionsStrip      (:1197-1213)
+ * d_flags[u] is the reference's PropagateResult, consistent | changed << 1;
+ * max_iters as lifeapi_stable_pass_batch_dev defines it (0 = 2^20; passes 0-3
+ * ignore it; | 4 when the bound stopped 4 / 5, the planes then the reference's
+ * after exactly max_iters iterations).  An inconsistent step or loop gives
+ * {false, false} = 0; passes 0 and 1 report {abort == 0, changes != 0} as the
+ * reference does, so 2 is possible there.  Planes are left exactly as the
+ * reference leaves them, every inconsistent early return included, and the
+ * strip passes differ from the full ones here: SynchroniseStateKnownStrip and
+ * UpdateOptionsStrip finish all their columns and then report the abort,
+ * SignalNeighboursStrip returns before writing, PropagateStepStrip stops at
+ * the first inconsistent pass.  A strip pass reads columns x-2 .. x+3 of the
+ * state and unknown planes and x-1 .. x+2 of the option planes (the torus),
+ * and writes inside x-2 .. x+3: a strip propagation stops where a full one
+ * would go on.                                                              */
+int lifeapi_stable_strip_pass_batch_dev(uint64_t *d_planes, const uint8_t *d_columns, uint8_t *d_flags,
+                                        size_t n, int pass, uint32_t max_iters, void *stream);
+/* d_planes[u].TestUnknowns(cells_u) (LifeStable.hpp:1321-1338, TestUnknown
+ * :1251-1284, Join :217-233), in place.  d_cells: 64 words (per_object_cells
+ * == 0) or n x 64.  The cells are visited in FirstOn() order (LifeAPI.hpp:
+ * 301-323) and what remains is narrowed by the new `unknown` after every
+ * cell, as the reference does: the result depends on that order.  TestUnknown
+ * with an inconsistent on-trial sets the cell off in the object itself and
+ * propagates there; if that fails too the object is left so and the result is
+ * {false, false}.
+ * d_flags[u] = consistent | changed << 1 (inconsistent: 0).  max_iters (0 =
+ * 2^20) bounds every PropagateStrip loop, each counted on its own; where it
+ * stops one, d_flags[u] = 4 and object u is not written at all (a half-run
+ * lookahead has no reference meaning).                                      */
+int lifeapi_stable_test_unknowns_batch_dev(uint64_t *d_planes, const uint64_t *d_cells, int per_object_cells,
+                                           uint8_t *d_flags, size_t n, uint32_t max_iters, void *stream);
+/* d_planes[u].PropagateAndTest() (LifeStable.hpp:163-184), in place:
+ * Propagate(), then TestUnknowns(Vulnerable().ZOI()), until neither changes.
+ * d_flags as above.  max_iters (0 = 2^20) bounds every Propagate loop, every
+ * PropagateStrip loop and the outer loop, each counted on its own; where it
+ * stops any, d_flags[u] = 4 and object u is not written at all.             */
+int lifeapi_stable_propagate_and_test_batch_dev(uint64_t *d_planes, uint8_t *d_flags, size_t n,
+                                                uint32_t max_iters, void *stream);
 /* LifeWeld::Step() (LifeWeld.hpp:169-186) `generations` times, in place on
  * LifeWeld[n] = {state, frozen2, frozen1, frozen0} x 64 words (the struct's
  * member order, LifeWeld.hpp:18-20); only the state planes change.        */
@@ -381,6 +440,14 @@ int lifeapi_weld_to_stable_batch(const uint64_t *welds, const uint64_t *active, 
                                  int device);
 int lifeapi_weld_interaction_offsets_batch(const uint64_t *welds, const uint64_t *other, uint64_t *out,
                                            size_t n, int device);
+/* host forms of the LifeStable lookahead entry points: the same arguments and
+ * the same checks, on host arrays                                           */
+int lifeapi_stable_strip_pass_batch(uint64_t *planes, const uint8_t *columns, uint8_t *flags, size_t n,
+                                    int pass, uint32_t max_iters, int device);
+int lifeapi_stable_test_unknowns_batch(uint64_t *planes, const uint64_t *cells, int per_object_cells,
+                                       uint8_t *flags, size_t n, uint32_t max_iters, int device);
+int lifeapi_stable_propagate_and_test_batch(uint64_t *planes, uint8_t *flags, size_t n, uint32_t max_iters,
+                                            int device);
 /* host form of lifeapi_step_contains_batch_dev: the search-loop idiom
  * "for g in 1..gens: s.Step(); if (s.Contains(target)) ..." (LifeAPI.hpp:
  * 1196-1216, LifeTarget.hpp:44-51) over n host universes; final (may be NULL,

@@ -812,6 +812,56 @@ int lifeapi_weld_interaction_offsets_batch(const uint64_t *welds, const uint64_t
                     });
 }
 
+// the LifeStable lookahead family: the argument checks that need no device
+namespace {
+int stable_test_check(const char *fn, const uint64_t *planes, const void *side, size_t side_bytes, bool side_align8,
+                      const uint8_t *flags, size_t n) {
+  if (!planes || !side || !flags) return fail(LIFEAPI_E_INVALID, "null pointer to %s", fn);
+  if (!aligned8(planes) || (side_align8 && !aligned8(side))) return fail(LIFEAPI_E_INVALID, "misaligned pointer to %s", fn);
+  if (ranges_overlap(planes, n * 5120, side, side_bytes) || ranges_overlap(planes, n * 5120, flags, n))
+    return fail(LIFEAPI_E_INVALID, "%s: an array overlaps the planes", fn);
+  return LIFEAPI_OK;
+}
+}  // namespace
+
+int lifeapi_stable_strip_pass_batch(uint64_t *planes, const uint8_t *columns, uint8_t *flags, size_t n, int pass,
+                                    uint32_t max_iters, int device) {
+  if (pass < 0 || pass > 5) return fail(LIFEAPI_E_INVALID, "lifeapi_stable_strip_pass_batch: pass outside 0..5%s");
+  if (n == 0) return LIFEAPI_OK;
+  const int rc = stable_test_check("lifeapi_stable_strip_pass_batch", planes, columns, n, false, flags, n);
+  if (rc != LIFEAPI_OK) return rc;
+  return host_batch(n, device, {{planes, planes, 5120}, {columns, nullptr, 1}, {nullptr, flags, 1}},
+                    [=](void *const *d, size_t m, hipStream_t s) {
+                      return lifeapi_stable_strip_pass_batch_dev((uint64_t *)d[0], (const uint8_t *)d[1],
+                                                                 (uint8_t *)d[2], m, pass, max_iters, s);
+                    });
+}
+
+int lifeapi_stable_test_unknowns_batch(uint64_t *planes, const uint64_t *cells, int per_object_cells, uint8_t *flags,
+                                       size_t n, uint32_t max_iters, int device) {
+  if (n == 0) return LIFEAPI_OK;
+  const bool per = per_object_cells != 0;
+  const int rc = stable_test_check("lifeapi_stable_test_unknowns_batch", planes, cells, per ? n * 512 : 512, true, flags, n);
+  if (rc != LIFEAPI_OK) return rc;
+  return host_batch(n, device, {{planes, planes, 5120}, {nullptr, flags, 1}, {cells, nullptr, 512, !per}},
+                    [=](void *const *d, size_t m, hipStream_t s) {
+                      return lifeapi_stable_test_unknowns_batch_dev((uint64_t *)d[0], (const uint64_t *)d[2], per,
+                                                                    (uint8_t *)d[1], m, max_iters, s);
+                    });
+}
+
+int lifeapi_stable_propagate_and_test_batch(uint64_t *planes, uint8_t *flags, size_t n, uint32_t max_iters,
+                                            int device) {
+  if (n == 0) return LIFEAPI_OK;
+  const int rc = stable_test_check("lifeapi_stable_propagate_and_test_batch", planes, flags, n, false, flags, n);
+  if (rc != LIFEAPI_OK) return rc;
+  return host_batch(n, device, {{planes, planes, 5120}, {nullptr, flags, 1}},
+                    [=](void *const *d, size_t m, hipStream_t s) {
+                      return lifeapi_stable_propagate_and_test_batch_dev((uint64_t *)d[0], (uint8_t *)d[1], m,
+                                                                         max_iters, s);
+                    });
+}
+
 int lifeapi_step_contains_batch(const uint64_t *in, uint64_t *final_states, const uint64_t *wanted,
                                 const uint64_t *unwanted, uint32_t *first_gen, size_t n,
                                 uint32_t generations, int device) {

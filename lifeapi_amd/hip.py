@@ -99,6 +99,12 @@ _SIGS = {
     "lifeapi_weld_to_target_batch": ([_vp, _vp, _vp, _sz, _int], _int),
     "lifeapi_weld_to_stable_batch": ([_vp, _vp, _int, _vp, _u32, _vp, _sz, _int], _int),
     "lifeapi_weld_interaction_offsets_batch": ([_vp, _vp, _vp, _sz, _int], _int),
+    "lifeapi_stable_strip_pass_batch_dev": ([_vp, _vp, _vp, _sz, _int, _u32, _vp], _int),
+    "lifeapi_stable_test_unknowns_batch_dev": ([_vp, _vp, _int, _vp, _sz, _u32, _vp], _int),
+    "lifeapi_stable_propagate_and_test_batch_dev": ([_vp, _vp, _sz, _u32, _vp], _int),
+    "lifeapi_stable_strip_pass_batch": ([_vp, _vp, _vp, _sz, _int, _u32, _int], _int),
+    "lifeapi_stable_test_unknowns_batch": ([_vp, _vp, _int, _vp, _sz, _u32, _int], _int),
+    "lifeapi_stable_propagate_and_test_batch": ([_vp, _vp, _sz, _u32, _int], _int),
 }
 for _name, (_args, _res) in _SIGS.items():
     _f = getattr(lib, _name)
@@ -749,6 +755,93 @@ def stable_vulnerable(planes: torch.Tensor, stream=None) -> torch.Tensor:
     out = torch.empty((n, N), dtype=torch.int64, device=planes.device)
     _check(lib.lifeapi_stable_vulnerable_batch_dev(planes.data_ptr(), out.data_ptr(), n, _stream(stream)))
     return out
+
+
+STABLE_STRIP_PASSES = ("sync_strip", "options_strip", "signal_strip", "step_strip", "propagate_strip",
+                       "stabilise_strip")
+
+
+def _strip_pass(which: str | int) -> int:
+    w = STABLE_STRIP_PASSES.index(which) if isinstance(which, str) else int(which)
+    if not 0 <= w < 6:
+        raise ValueError("which must name one of STABLE_STRIP_PASSES")
+    return w
+
+
+def stable_strip_pass(planes: torch.Tensor, columns: torch.Tensor, which: str | int, max_iters: int = 0,
+                      stream=None) -> torch.Tensor:
+    """LifeStable strip pass (LifeStable.hpp:921-948, 995-1249) in place on (n,
+    10*64) planes, object u at column ``columns[u]`` (uint8, 0..63); returns
+    uint8 flags (bit0 consistent, bit1 changed, bit2 stopped by max_iters)."""
+    w = _strip_pass(which)
+    n = _planes(planes, 10, "planes")
+    if not columns.is_cuda or columns.dtype != torch.uint8 or not columns.is_contiguous() or columns.numel() != n:
+        raise ValueError("columns must be a contiguous uint8 device tensor with one column per object")
+    flags = torch.empty(n, dtype=torch.uint8, device=planes.device)
+    _check(lib.lifeapi_stable_strip_pass_batch_dev(planes.data_ptr(), columns.data_ptr(), flags.data_ptr(), n, w,
+                                                   max_iters, _stream(stream)))
+    return flags
+
+
+def stable_test_unknowns(planes: torch.Tensor, cells: torch.Tensor, max_iters: int = 0, stream=None) -> torch.Tensor:
+    """``TestUnknowns(cells)`` (LifeStable.hpp:1321-1338) in place on (n, 10*64)
+    planes; ``cells`` holds one universe for the whole batch or one per object.
+    Returns uint8 flags: consistent | changed << 1, or 4 where ``max_iters``
+    stopped a PropagateStrip (that object is then left as it was)."""
+    n = _planes(planes, 10, "planes")
+    per = _one_or_n(cells, n, "cells")
+    flags = torch.empty(n, dtype=torch.uint8, device=planes.device)
+    _check(lib.lifeapi_stable_test_unknowns_batch_dev(planes.data_ptr(), cells.data_ptr(), per, flags.data_ptr(), n,
+                                                      max_iters, _stream(stream)))
+    return flags
+
+
+def stable_propagate_and_test(planes: torch.Tensor, max_iters: int = 0, stream=None) -> torch.Tensor:
+    """``PropagateAndTest()`` (LifeStable.hpp:163-184) in place on (n, 10*64)
+    planes: Propagate, then TestUnknowns(Vulnerable().ZOI()), until neither
+    changes.  Returns uint8 flags: consistent | changed << 1, or 4 where
+    ``max_iters`` stopped a loop (that object is then left as it was)."""
+    n = _planes(planes, 10, "planes")
+    flags = torch.empty(n, dtype=torch.uint8, device=planes.device)
+    _check(lib.lifeapi_stable_propagate_and_test_batch_dev(planes.data_ptr(), flags.data_ptr(), n, max_iters,
+                                                           _stream(stream)))
+    return flags
+
+
+def stable_strip_pass_host(planes: np.ndarray, columns: np.ndarray, which: str | int, max_iters: int = 0,
+                           device: int = 0) -> tuple[np.ndarray, np.ndarray]:
+    """Host-pointer ``lifeapi_stable_strip_pass_batch``: (planes, flags), the input untouched."""
+    w = _strip_pass(which)
+    src, n = _host_planes(planes, 10, "planes")
+    col = np.ascontiguousarray(columns, dtype=np.uint8)
+    if col.size != n:
+        raise ValueError("columns must hold one column per object")
+    out, flags = src.reshape(n, 10 * N).copy(), np.empty(n, dtype=np.uint8)
+    _check(lib.lifeapi_stable_strip_pass_batch(out.ctypes.data, col.ctypes.data, flags.ctypes.data, n, w, max_iters,
+                                               device))
+    return out, flags
+
+
+def stable_test_unknowns_host(planes: np.ndarray, cells: np.ndarray, max_iters: int = 0,
+                              device: int = 0) -> tuple[np.ndarray, np.ndarray]:
+    """Host-pointer ``lifeapi_stable_test_unknowns_batch``: (planes, flags), the input untouched."""
+    src, n = _host_planes(planes, 10, "planes")
+    cel = _host_u64(cells)
+    if cel.size // N not in (1, n):
+        raise ValueError("cells must hold one universe or one per object")
+    out, flags = src.reshape(n, 10 * N).copy(), np.empty(n, dtype=np.uint8)
+    _check(lib.lifeapi_stable_test_unknowns_batch(out.ctypes.data, cel.ctypes.data, int(cel.size // N == n and n != 1),
+                                                  flags.ctypes.data, n, max_iters, device))
+    return out, flags
+
+
+def stable_propagate_and_test_host(planes: np.ndarray, max_iters: int = 0,
+                                   device: int = 0) -> tuple[np.ndarray, np.ndarray]:
+    """Host-pointer ``lifeapi_stable_propagate_and_test_batch``: (planes, flags), the input untouched."""
+    src, n = _host_planes(planes, 10, "planes")
+    out, flags = src.reshape(n, 10 * N).copy(), np.empty(n, dtype=np.uint8)
+    _check(lib.lifeapi_stable_propagate_and_test_batch(out.ctypes.data, flags.ctypes.data, n, max_iters, device))
+    return out, flags
 
 
 def neighbour_count(states: torch.Tensor, stream=None) -> torch.Tensor:
