@@ -11,7 +11,8 @@ Object i of the family (numpy's frozen RandomState stream, seeded by i):
   * in one object of five, one cell of the pattern's boundary wrongly SetOn.
 tests/golden/make_stable_test_golden.py draws the family, classifies it on the
 reference's outputs and keeps the indices in tests/golden/stable_test.npz
-(`kept`); the tests rebuild those objects here.
+(`kept`); the tests rebuild those objects here.  `dense` draws a second family
+that is not recorded; the numpy model alone judges it.
 
 A LifeStable is (10, 64) uint64: {state, unknown, live2, live3, dead0, dead1,
 dead2, dead4, dead5, dead6}, word x = column x, bit y = row y, option planes
@@ -110,6 +111,40 @@ def one(i):
     info = {"name": name, "dx": int(dx), "dy": int(dy), "region": int(which), "wrong": wrong,
             "straddles": bool(p[63].any() and p[0].any())}
     return planes, int(dx % 64), info
+
+
+def dense(i):
+    """object i (< DENSE_DRAWN) of a second family, not recorded: more of the neighbourhood
+    known (density 0.4 .. 0.85), never the whole torus unknown, no wrong cell.  Its lookaheads
+    are short and its PropagateAndTest takes many rounds, so a `max_iters` can run out in the
+    outer loop before any inner loop reaches it (DENSE_OUTER): no object of the first family
+    does that.  (planes (10, 64) uint64, column, info)"""
+    rs = np.random.RandomState(1000003 * (i + 1) + 7)
+    name = NAMES[i % len(NAMES)]
+    dx, dy = rs.randint(64), rs.randint(64)
+    p = np.zeros((64, 64), bool)
+    for x, y in cells(STILL_LIFES[name]):
+        p[(x + dx) % 64, (y + dy) % 64] = True
+    density = (0.4, 0.55, 0.7, 0.85)[rs.randint(4)]
+    z1 = zoi(p)
+    z2 = zoi(z1)
+    z3 = zoi(z2)
+    known = (rs.random_sample((64, 64)) < density) & z3
+    which = rs.randint(3)
+    region = (z1, z2, z3)[which]
+    on = known & p
+    off = ~region | (known & ~p)
+    unknown = region & ~known
+    planes = np.stack([pack(on), pack(unknown), pack(off), pack(off)] + [pack(on)] * 6)
+    return planes, int(dx), {"name": name, "dx": int(dx), "dy": int(dy), "region": int(which)}
+
+
+DENSE_DRAWN = 4000
+# (object, max_iters) of the second family at which PropagateAndTest's outer loop runs out: that
+# many rounds each change something and no Propagate or PropagateStrip in them needs more
+# iterations (found by running the model unbounded over the whole family and comparing each
+# object's rounds with the iterations of its deepest inner loop so far)
+DENSE_OUTER = ((1918, 6), (1881, 7), (1881, 8), (1881, 9))
 
 
 def build(indices):

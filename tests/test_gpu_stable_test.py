@@ -4,7 +4,9 @@ for bit, planes and flags, and against the CPU model (tests/
 test_stable_test_model.py, itself pinned to the same recording).  The ragged
 batches compare against the recording of the pool's objects, which the model
 equals object by object (test_propagate_and_test_matches_the_recording), so the
-model's eight seconds are spent once, on the CPU."""
+model's eight seconds are spent once, on the CPU.  The bounded forms
+(`max_iters`) have no recording; the model's bounded answers are computed once
+per process (M.bounded_*, some twenty seconds) and shared by their tests."""
 import numpy as np
 import pytest
 import torch
@@ -21,7 +23,7 @@ SENTINEL = np.uint64(0xA5A5A5A5A5A5A5A5)
 
 @pytest.fixture(scope="module")
 def rec():
-    return M.Recording()
+    return M.recording()
 
 
 class Guarded:
@@ -224,3 +226,134 @@ def test_bound(hip, rec, port):
     g = Guarded(rec.planes[pick])
     fl = host_flags(hip.stable_propagate_and_test(g.out, max_iters=0))
     assert (fl == rec.pat_flags[pick]).all() and (g.result() == rec.pat[pick]).all()
+
+
+# ---- the bound, bit for bit -------------------------------------------------------------
+# against the model's bounded forms (test_stable_test_model.py bounded_*: computed once per
+# process, pinned and proved non-vacuous there without a GPU)
+
+def strip_run(hip, planes, columns, which, max_iters=0):
+    g = Guarded(planes)
+    cols = torch.from_numpy(np.ascontiguousarray(columns, np.uint8).reshape(-1)).cuda()
+    fl = host_flags(hip.stable_strip_pass(g.out, cols, which, max_iters=max_iters))
+    return g.result(), fl
+
+
+@pytest.fixture(scope="module")
+def own():
+    return M.own_strips()
+
+
+@pytest.mark.parametrize("k", M.BOUNDS)
+@pytest.mark.parametrize("which", (4, 5))
+def test_bounded_strip_loops(hip, own, which, k):
+    """PropagateStrip and StabiliseOptionsStrip under max_iters = 1 .. 4: flags 7 and the planes
+    after exactly k iterations where the bound stops the loop (k_stable_strip stores them), the
+    unbounded answer where it does not; at 4 nothing is stopped"""
+    starts, columns, _ = own
+    planes, flags = M.bounded_strips()[which, k]
+    got, fl = strip_run(hip, starts, columns, which, k)
+    assert (fl == flags).all(), np.flatnonzero(fl != flags)
+    assert (got == planes).all(), np.flatnonzero((got != planes).any(axis=(1, 2)))
+    # (at 1 every loop that changes anything is stopped: its confirming iteration has not run)
+    assert (fl == 7).any() == (k < 4) and (fl == 0).any() and (fl == 1).any() and (fl == 3).any() == (k > 1)
+
+
+def test_bounded_strip_loop_at_fixed_columns(hip, own):
+    """PropagateStrip under max_iters = 2 at columns 0, 1, 2, 31, 61, 62, 63 of every object"""
+    starts = own[0]
+    planes, flags = M.bounded_strips()["columns"]
+    got, fl = strip_run(hip, np.repeat(starts[:, None], 7, axis=1), np.tile(C.STRIP_COLUMNS, len(starts)), 4, 2)
+    assert (fl == flags.reshape(-1)).all()
+    assert (got == planes.reshape(-1, 10, 64)).all()
+    assert (fl == 7).sum() >= 8
+
+
+@pytest.mark.parametrize("which", range(4))
+def test_single_strip_passes_ignore_the_bound(hip, own, which):
+    starts, columns, want = own
+    got, fl = strip_run(hip, starts, columns, which, 1)
+    assert (fl == want[which][1]).all() and (got == want[which][0]).all()
+    free, ffl = strip_run(hip, starts, columns, which, 0)
+    assert (fl == ffl).all() and (got == free).all()
+
+
+@pytest.mark.parametrize("which", range(6))
+def test_strip_column_high_bits(hip, own, which):
+    """only the low six bits of a column count"""
+    starts, columns, want = own
+    for high in (0x40, 0x80, 0xC0):
+        got, fl = strip_run(hip, starts, columns | np.uint8(high), which)
+        assert (fl == want[which][1]).all(), high
+        assert (got == want[which][0]).all(), high
+    assert len(set(columns.tolist())) == 64
+
+
+def sandwich(stopped):
+    """an order of the rows in which unstopped and stopped ones take turns for as long as both
+    last: a stopped object then lies between two that are written"""
+    s, f = list(np.flatnonzero(stopped)), list(np.flatnonzero(~stopped))
+    order = []
+    while s and f:
+        order += [f.pop(0), s.pop(0)]
+    return np.array(order + f + s)
+
+
+@pytest.mark.parametrize("k", M.BOUNDS)
+@pytest.mark.parametrize("form", ("per", "one"))
+def test_bounded_test_unknowns(hip, port, form, k):
+    """TestUnknowns under max_iters = 1 .. 4, the cells per object and one universe for all: an
+    object that the bound stops -- at its first cell, or at a later one after earlier cells have
+    changed it in registers -- returns 4 and keeps every byte; the objects around it are the
+    model's"""
+    b = M.bounded_unknowns(port)
+    planes, flags, stops = b.want[form, k]
+    order = sandwich(flags == 4)
+    g = Guarded(b.after[order])
+    cells = dev(b.per[order]) if form == "per" else dev(b.one[None])
+    fl = host_flags(hip.stable_test_unknowns(g.out, cells, max_iters=k))
+    got = g.result()
+    assert (fl == flags[order]).all(), order[fl != flags[order]]
+    assert (got == planes[order]).all(), order[(got != planes[order]).any(axis=(1, 2))]
+    first, later = M.stop_cells([stops[j] for j in order])
+    assert len(first) >= 2 and (len(later) >= 2 or k == 1)
+    for rows in (first, later):
+        assert (fl[rows] == 4).all() and (got[rows] == b.after[order][rows]).all()
+    inside = np.flatnonzero(fl[1:-1] == 4) + 1
+    assert ((fl[inside - 1] != 4) & (fl[inside + 1] != 4)).sum() >= 2
+
+
+@pytest.mark.parametrize("k", M.PAT_BOUNDS + (11,))
+def test_bounded_propagate_and_test(hip, port, k):
+    """PropagateAndTest under max_iters = k: wherever the bound stops the run -- the first
+    Propagate, a later one, a PropagateStrip at the first or a later cell of any round, the
+    outer loop -- the object returns 4 and keeps every byte, next to objects that finish; the
+    same device batch, run again without a bound, is the unbounded answer.  At 10 and 11
+    nothing is stopped."""
+    b = M.bounded_propagate_and_test(port)
+    planes, flags, ends = b.want[k] if k in b.want else (*b.free, None)
+    order = sandwich(flags == 4)
+    g = Guarded(b.given[order])
+    fl = host_flags(hip.stable_propagate_and_test(g.out, max_iters=k))
+    got = g.result()
+    assert (fl == flags[order]).all(), order[fl != flags[order]]
+    assert (got == planes[order]).all(), order[(got != planes[order]).any(axis=(1, 2))]
+    stopped = fl == 4
+    if k >= 10:
+        assert not stopped.any() and (fl == b.free[1][order]).all() and (got == b.free[0][order]).all()
+        return
+    sites = {}
+    for row, j in enumerate(order):
+        if ends[j]["site"] != "finished":
+            sites.setdefault((ends[j]["site"], min(ends[j]["round"], 2), ends[j]["cells"] > 0), []).append(row)
+    assert sites and sum(map(len, sites.values())) == stopped.sum()
+    for site, rows in sites.items():
+        assert (fl[rows] == 4).all() and (got[rows] == b.given[order][rows]).all(), site
+    fl2 = host_flags(hip.stable_propagate_and_test(g.out))
+    again = g.result()
+    assert (fl2[stopped] == b.free[1][order][stopped]).all()
+    assert (again[stopped] == b.free[0][order][stopped]).all()
+    # (a finished, consistent object is a fixpoint of PropagateAndTest: its last round changed nothing)
+    done = ~stopped & (fl != 0)
+    assert (fl2[done] == 1).all() and (again[done] == got[done]).all()
+

@@ -147,6 +147,72 @@ def test_sharded_host_forms(hip, shards, k):
     host_twice(stable)
 
 
+@pytest.mark.parametrize("device", [0, -1])
+def test_sharded_stable_lookahead_host_forms(hip, port, shards, device):
+    """The host-pointer forms of the LifeStable lookahead family on 67 objects,
+    on one device (two chunks) and in three shards: the 1-byte `columns` and
+    `flags`, the per-object `cells` and the one `cells` for the whole batch cut
+    where the chunks and shards are cut, every object with a column, a mask and
+    an answer of its own; `pass` and `max_iters` as given -- at max_iters = 2
+    the model's flags 7 and 4, which the unbounded call does not give.  Against
+    the recording and the model (tests/test_stable_test_model.py)."""
+    import test_stable_test_model as M
+    shards(3)
+    rec, n = M.recording(), 67
+    strips = M.bounded_strips()
+    starts, columns, recorded = M.own_strips()
+    # the strip passes: by turns a row that pass 0 changes, one that max_iters = 2 stops in pass 4,
+    # and any other
+    rng = np.random.default_rng(67)
+    slow = np.flatnonzero(strips[4, 2][1] == 7)
+    rows = rng.permutation(np.setdiff1d(np.arange(len(starts)), slow))[:n]
+    rows[0::3] = rng.permutation(np.flatnonzero(recorded[0][1] == 3))[:len(rows[0::3])]
+    rows[1::3] = slow[:len(rows[1::3])]
+    thirds = ((0, 22), (22, 44), (44, 67))
+    assert len(set(columns[rows].tolist())) >= 24
+    given = starts[rows].copy()
+    for which in range(6):
+        want = recorded[which][0][rows]
+        got, fl = hip.stable_strip_pass_host(given, columns[rows], which, device=device)
+        assert (fl == recorded[which][1][rows]).all(), which
+        assert (got.reshape(n, 10, 64) == want).all(), which
+        same = (want == given).all(axis=(1, 2))
+        assert all(same[a:c].any() and not same[a:c].all() for a, c in thirds), which
+    for which in (4, 5):
+        planes, flags = strips[which, 2]
+        got, fl = hip.stable_strip_pass_host(given, columns[rows], which, max_iters=2, device=device)
+        assert (fl == flags[rows]).all() and (got.reshape(n, 10, 64) == planes[rows]).all(), which
+        assert all((fl[a:c] == 7).any() for a, c in thirds), which
+    assert (given == starts[rows]).all()
+    # TestUnknowns: each object's own cells, and one universe of cells for all
+    b = M.bounded_unknowns(port)
+    rows = np.arange(n) % len(b.pick)
+    after = b.after[rows].copy()
+    assert len(b.pick) < n and len({m.tobytes() for m in b.per}) >= 48
+    got, fl = hip.stable_test_unknowns_host(after, b.per[rows], device=device)
+    assert (fl == rec.tu_flags[b.pick][rows]).all() and (got.reshape(n, 10, 64) == rec.tu[b.pick][rows]).all()
+    assert not (fl == 4).any() and (fl == 3).any()
+    for form, cells in (("per", b.per[rows]), ("one", b.one)):
+        planes, flags, _ = b.want[form, 2]
+        got, fl = hip.stable_test_unknowns_host(after, cells, max_iters=2, device=device)
+        assert (fl == flags[rows]).all() and (got.reshape(n, 10, 64) == planes[rows]).all(), form
+        assert all((fl[a:c] == 4).any() and (fl[a:c] != 4).any() for a, c in thirds), form
+    assert (after == b.after[rows]).all()
+    # PropagateAndTest
+    p = M.bounded_propagate_and_test(port)
+    rows = np.arange(0, len(p.given), 3)
+    assert len(rows) == n
+    given = p.given[rows].copy()
+    got, fl = hip.stable_propagate_and_test_host(given, device=device)
+    assert (fl == p.free[1][rows]).all() and (got.reshape(n, 10, 64) == p.free[0][rows]).all()
+    assert not (fl == 4).any()
+    planes, flags, _ = p.want[2]
+    got, fl = hip.stable_propagate_and_test_host(given, max_iters=2, device=device)
+    assert (fl == flags[rows]).all() and (got.reshape(n, 10, 64) == planes[rows]).all()
+    assert all((fl[a:c] == 4).any() and (fl[a:c] != 4).any() for a, c in thirds)
+    assert (given == p.given[rows]).all()
+
+
 def _block_and_ring():
     blk, ring = np.zeros(64, np.uint64), np.zeros(64, np.uint64)
     blk[20] = blk[21] = np.uint64(0b11 << 30)

@@ -4,7 +4,9 @@ second call on the same batch or a stream of the caller's own reaches.
 * A -- the later chunks of every capped grid (step.hip, reduce.hip,
   cone_launch.hpp): a wave of k_cone_adapt, k_pop<kRedU> or the merged split
   kernel takes a second chunk only once the batch exceeds blocks per CU x CUs
-  x 4 waves x universes per chunk, which no other test's batch does;
+  x 4 waves x universes per chunk, which no other test's batch does; and the
+  second object of a wave of k_stable_strip (stable_test.hip), past blocks per
+  CU x CUs x 4 objects;
 * B -- the reversed launch order of k_weld, k_step_contains<8> and k_step
   (host.hip launch_reverse), with the order of every launch asserted through
   the book (the tuning build's order_probe / order_note);
@@ -389,6 +391,56 @@ def test_iterated_filter_later_chunks(hip, lim, filter_batch, gens):
             got = first.cpu().numpy().astype(np.uint32)
             bad = np.nonzero(got != want)[0]
             assert bad.size == 0, (name, gens, align, bad.size, bad[:8], got[bad[:8]], want[bad[:8]])
+
+
+# ---- A4: the LifeStable strip passes' loop ----------------------------------
+
+@pytest.fixture(scope="module")
+def strip_batch(hip, lim):
+    """One pass of k_stable_strip's grid (kBlocksPerCu blocks per CU, a wave per
+    object) plus 4097 objects, drawn from the recorded objects and starts: the
+    first pass by seeded permutations of all 512, the later objects each a
+    seeded, nonzero step away from the object its wave took first -- so no
+    wave's second object is its first and no period of the batch meets the
+    grid's.  (pick, first pass, starts, columns on the device, recorded planes
+    and flags per pass)"""
+    import test_stable_test_model as M
+    starts, own_columns, want = M.own_strips()
+    pool = len(starts)
+    first_pass = lim.waves(source_constant("kBlocksPerCu"))
+    rng = np.random.default_rng(8192)
+    pick = np.concatenate([rng.permutation(pool) for _ in range(-(-first_pass // pool))])[:first_pass]
+    pick = np.concatenate([pick, (pick[:4097] + rng.integers(1, pool, 4097)) % pool])
+    columns = torch.from_numpy(own_columns[pick]).cuda()
+    return pick, first_pass, starts, columns, want
+
+
+@pytest.mark.parametrize("which", range(6))
+def test_stable_strip_later_objects(hip, strip_batch, which):
+    """The six strip passes on more objects than k_stable_strip's capped grid
+    has waves (Grid{n, kBlocksPerCu}): 4097 waves take a second object, the
+    others one.  Every object's planes and flags against the reference's
+    recording; the second objects hold every flag the pass can give.
+    (k_stable_test's loop is out of a test's reach: its grid is Grid{n}, one
+    wave per object, and runs the loop again only where launch() has to cap it
+    at 2^30 blocks.)"""
+    from test_gpu_stable_test import Guarded
+    pick, first_pass, starts, columns, want = strip_batch
+    planes, flags = want[which]
+    assert len(pick) == first_pass + 4097 and (pick[first_pass:] != pick[:4097]).all()
+    later = set(flags[pick[first_pass:]].tolist())
+    assert later == set(flags.tolist()) and later >= ({1, 3} if which == 1 else {0, 1, 3}), later
+    g = Guarded(starts[pick])
+    fl = hip.stable_strip_pass(g.out, columns, which)
+    torch.cuda.synchronize()
+    fl = fl.cpu().numpy()
+    bad = np.nonzero(fl != flags[pick])[0]
+    assert bad.size == 0, (which, bad.size, bad[:8])
+    got = g.result()
+    bad = np.nonzero((got != planes[pick]).any(axis=(1, 2)))[0]
+    assert bad.size == 0, (which, bad.size, bad[:8])
+    del g
+    torch.cuda.empty_cache()
 
 
 # ---- B: the order of every launch, asserted --------------------------------
