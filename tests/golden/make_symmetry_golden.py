@@ -4,8 +4,10 @@ Symmetricize, XYBounds, SymmetryOrbit and SymmetryOrbitRepresentatives
 inputs that tests/test_symmetry_model.py builds.  CPU only; run from the
 repository root where the reference's headers are:
 
-    python tests/golden/make_symmetry_golden.py [--ref DIR]
+    python tests/golden/make_symmetry_golden.py [--ref DIR] [--only-sweeps]
 
+--only-sweeps records tests/golden/symmetry_sweeps.npz alone (the shift,
+offset, bounding-box and stabiliser sweeps) and leaves symmetry.npz as it is.
 symmetry_ref_shim.cpp is compiled against those headers where they lie, into a
 temporary directory, with the flags of make_match_golden.py.  Only data is
 stored: the reference's outputs and the moved orbit inputs; the seeded random
@@ -69,11 +71,61 @@ def distinct(arrays):
     return all((a != b).any() for a, b in itertools.combinations(arrays, 2))
 
 
+def record_sweeps(ref, port):
+    """tests/golden/symmetry_sweeps.npz: the reference on the sweeps of
+    tests/test_symmetry_model.py.  Landing coordinates, bounds, masks and
+    images of a few cells: all of it compresses to little."""
+    syms = list(M.SYMMETRIES.values())
+    r5, pairs, states = M.symmetricize_states(port)[0], M.pair_states(), M.orbit_sweep_states()
+    with tempfile.TemporaryDirectory() as tmp:
+        exe = compile_shim(ref, tmp)
+        moved = reference(exe, tmp, [(TRANSFORM, t, dx, dy, M.cell(*M.SWEEP_CELL)) for t in range(16)
+                                     for dx, dy in M.SHIFTS])
+        landing = np.array([M.where(s) for s in moved], np.uint8).reshape(16, len(M.SHIFTS), 2)
+        sy = np.stack(reference(exe, tmp, [(SYMMETRICIZE, y, dx, dy, r5) for y in syms for dx, dy in M.SYM_SWEEP]))
+        sy = sy.reshape(len(syms), len(M.SYM_SWEEP), 64)
+        po = np.stack(reference(exe, tmp, [(ORBIT, 0, 0, 0, s) for s in pairs]))
+        so = np.stack(reference(exe, tmp, [(ORBIT, 0, 0, 0, s) for s in states]))
+    assert (po[:, :64] == pairs).all() and (so[:, :64] == states).all()
+    pair_bounds, pair_mask = po[:, 64:68].view(np.int64).astype(np.int8), po[:, -1].astype(np.uint8)
+    orbit_bounds, orbit_mask = so[:, 64:68].view(np.int64).astype(np.int8), so[:, -1].astype(np.uint8)
+    orbit_images = so[:, 68:68 + 512].reshape(len(states), 8, 64)
+
+    # ---- non-vacuity, on the reference's outputs alone ----
+    at = 0
+    for name, sweep in M.SHIFT_SWEEPS.items():   # every residue of a sweep lands the cell somewhere else
+        for t in range(16):
+            assert len({tuple(c) for c in landing[t, at:at + 64].tolist()}) == 64, (name, M.TRANSFORMS[t])
+        at += 64
+    c1 = syms.index(M.SYMMETRIES["C1"])
+    for k in range(len(syms)):
+        for part in (sy[k, :141], sy[k, 141:]):   # a line's offsets matter (D4diag halves them: 32 results)
+            assert k == c1 or len({p.tobytes() for p in part}) >= 32, syms[k]
+    stab = orbit_mask[:3 * len(M.SUBGROUPS) + len(syms)]
+    assert set(M.STABILISER_MASKS) <= set(stab.tolist()), sorted(set(stab.tolist()))
+    assert len({tuple(b) for b in pair_bounds.tolist()}) >= 4000
+    assert (orbit_mask[-2:] == 0xFF).all() and (orbit_bounds[-2:] == (-20, -20, 19, 19)).all()
+
+    path = os.path.join(HERE, "symmetry_sweeps.npz")
+    np.savez_compressed(path, shift_landing=landing, symmetricize_sweep=sy, pair_bounds=pair_bounds,
+                        pair_mask=pair_mask, orbit_bounds=orbit_bounds, orbit_mask=orbit_mask,
+                        orbit_images=orbit_images)
+    size = os.path.getsize(path)
+    assert size <= 512 << 10, size
+    print(f"{path}: {size} bytes; 16 transforms x {len(M.SHIFTS)} shifts, {len(syms)} symmetries x "
+          f"{len(M.SYM_SWEEP)} offsets, {len(pairs)} pairs, {len(states)} orbits; pair masks "
+          f"{sorted(set(pair_mask.tolist()))}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ref", default="/root/reference")
+    ap.add_argument("--only-sweeps", action="store_true", help="record symmetry_sweeps.npz alone")
     args = ap.parse_args()
     port = Port()
+    record_sweeps(args.ref, port)
+    if args.only_sweeps:
+        return
     ts, ss, bases = M.transform_states(port), M.symmetricize_states(port), M.orbit_bases(port)
     syms = list(M.SYMMETRIES.values())
     with tempfile.TemporaryDirectory() as tmp:

@@ -2,7 +2,13 @@
 (symmetry_kernels.hpp) through lifeapi_amd.hip, bit-exact against (1) the
 reference's recorded outputs (tests/golden/symmetry.npz) and (2) the numpy
 definitions of tests/test_symmetry_model.py, which CPU tests pin to the same
-fixture; then group properties on the GPU alone."""
+fixture; then group properties on the GPU alone.
+
+The sweeps (tests/golden/symmetry_sweeps.npz and the builders of the model's
+file) run every residue of a shift through k_transform, every offset of two
+lines through k_symmetricize's ds_bpermute path, every pair of populated
+columns and rows through k_bounds and the orbit's per-image maps, and a state
+of every stabiliser subgroup of D4 through the orbit's comparison."""
 import os
 import subprocess
 
@@ -18,7 +24,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 RAGGED = [1, 2, 3, 5, 63, 64, 65, 4097]
 MOVE = (13, -27)                                   # the ragged batches' (dx, dy)
-RAGGED_SYMMETRIES = {"C4": (7, -3), "D4diag": (-40, 13), "D2AcrossX": (5, 6)}   # with odd x - y for D4diag
+# every symmetry Symmetricize defines, one offset each: odd x - y for D4diag, components below -64 and at 64
+RAGGED_SYMMETRIES = {"C4": (7, -3), "D4diag": (-40, 13), "D2AcrossX": (5, 6), "C1": (3, 4), "D2AcrossY": (-70, 9),
+                     "D2negdiagodd": (12, -65), "D2diagodd": (-1, 33), "C2": (31, -32), "D4": (-67, 64)}
+assert set(RAGGED_SYMMETRIES) == set(M.SYMMETRIES)
+PLANTED = 60                                       # the every-7th slot the stabiliser states start at
 
 
 @pytest.fixture(scope="module")
@@ -29,21 +39,24 @@ def gold():
 @pytest.fixture(scope="module")
 def ragged(port):
     """4097 seeded universes, alternating full and quarter density, every 7th
-    a small pattern of the golden's list, some of them on the window's seam;
-    and the numpy definitions' answers, computed once.  A batch of n is the
-    first n of them."""
+    a small pattern of the golden's list, some of them on the window's seam,
+    or (slots 60 .. 100, which repeat slots 0 .. 40) a state of each
+    stabiliser subgroup of D4; and the numpy definitions' answers, computed
+    once.  A batch of n is the first n of them."""
     x = port.fill(4097, seed=3030)
     x[1::2] &= port.fill(4097, seed=3031)[1::2] & port.fill(4097, seed=3032)[1::2]
     bases = M.orbit_bases(port)[:len(M.PATTERNS)]
     spots = ((0, 0), (30, 31), (-2, -1), (31, 5), (7, 30), (40, 50))
     for k, u in enumerate(range(0, 4097, 7)):
         x[u] = M.np_transform(bases[k % len(bases)], 0, *spots[(k // len(bases)) % len(spots)])
+    planted = M.stabiliser_states()
+    x[7 * PLANTED:7 * (PLANTED + len(planted)):7] = planted
     want = {("transform", t): M.np_transform_batch(x, t, *MOVE) for t in range(16)}
     for name, off in RAGGED_SYMMETRIES.items():
         want["symmetricize", name] = M.np_symmetricize(x, M.SYMMETRIES[name], *off)
     want["bounds"] = M.np_bounds_batch(x)
     want["images"], want["mask"] = M.np_orbit_batch(x)
-    assert len(set(want["mask"].tolist())) >= 5, sorted(set(want["mask"].tolist()))
+    assert set(M.STABILISER_MASKS) <= set(want["mask"].tolist()), sorted(set(want["mask"].tolist()))
     for a in (x, *want.values()):
         a.flags.writeable = False
     return x, want
@@ -182,6 +195,125 @@ def test_host_forms(hip, ragged, monkeypatch, device, shards):
     assert (images == want["images"]).all() and (mask == want["mask"]).all()
     assert (hip.symmetry_orbit_host(x, images=False, device=device) == want["mask"]).all()
     assert (hip.symmetry_orbit_host(x, first=False, device=device) == want["images"]).all()
+
+
+# ---- the sweeps: every residue, offset, box and stabiliser -----------------------
+
+@pytest.fixture(scope="module")
+def sweeps():
+    return dict(np.load(M.SWEEPS))
+
+
+@pytest.fixture(scope="module")
+def five(port):
+    """one wave's group of four and a tail of one: a full-density state, one
+    ANDed down to 1/8, the cell (17, 42), a glider across rows 31 | 32 and
+    columns 31 | 32, and the empty state"""
+    eighth = port.fill(1, seed=5051) & port.fill(1, seed=5052) & port.fill(1, seed=5053)
+    glider = M.np_transform(port.parse(M.PATTERNS["glider"]), 0, 30, 31)
+    x = np.stack([port.fill(1, seed=5050)[0], eighth[0], M.cell(*M.SWEEP_CELL), glider, np.zeros(64, np.uint64)])
+    x.flags.writeable = False
+    return x
+
+
+def first_difference(got, want, cases):
+    bad = np.argwhere((got != want).reshape(len(cases), -1).any(axis=1))
+    return None if len(bad) == 0 else (len(bad), cases[int(bad[0][0])])
+
+
+def test_transform_every_residue(hip, five, sweeps):
+    """every transform at every residue of dx, of dy and of both, and at moves
+    far out of range: each launch writes its slice of one buffer, which is
+    compared once.  The single cell must land where the reference put it, the
+    other four universes where the model does.  In place at the residues
+    around the half swap and at both ends."""
+    cases = [(t, dx, dy) for t in range(16) for dx, dy in M.SHIFTS]
+    want = np.stack([M.np_transform_batch(five, *c) for c in cases])
+    for (t, dx, dy), w, at in zip(cases, want, sweeps["shift_landing"].reshape(-1, 2)):
+        assert (w[2] == M.cell(*at.tolist())).all(), (M.TRANSFORMS[t], dx, dy)      # the model is the recording
+    s = to_dev(five)
+    out = torch.empty((len(cases), 5, 64), dtype=torch.int64, device="cuda")
+    for k, (t, dx, dy) in enumerate(cases):
+        hip.transform(s, t, dx, dy, out=out[k])
+    assert first_difference(to_host(out), want, cases) is None
+    assert (to_host(s) == five).all()
+    again = [k for k, (t, dx, dy) in enumerate(cases)
+             if any((dx, dy) == sweep[j] for sweep in M.SHIFT_SWEEPS.values() for j in M.IN_PLACE_K)]
+    assert len(again) == 16 * 3 * len(M.IN_PLACE_K)
+    out = s.unsqueeze(0).repeat(len(again), 1, 1)
+    for k, v in zip(again, out.unbind(0)):
+        assert hip.transform(v, *cases[k], out=v) is v
+    assert first_difference(to_host(out), want[again], [cases[k] for k in again]) is None
+
+
+def test_symmetricize_every_offset(hip, port, five, sweeps):
+    """the 8 symmetries that do something at (dx, 13), dx = -70 .. 70, and at
+    (-40, dy), dy = -70 .. 70, on the five universes and, sixth, the moved
+    R-pentomino the reference was recorded on: that one is compared with the
+    recording, the rest with the model"""
+    r5 = M.symmetricize_states(port)[0]
+    x = np.concatenate([five, r5[None]])
+    names = [name for name in M.SYMMETRIES if name != "C1"]
+    cases = [(name, dx, dy) for name in names for dx, dy in M.SYM_SWEEP]
+    want = np.stack([M.np_symmetricize(x, M.SYMMETRIES[name], dx, dy) for name, dx, dy in cases])
+    recorded = np.stack([sweeps["symmetricize_sweep"][list(M.SYMMETRIES).index(name)] for name in names])
+    want[:, 5] = recorded.reshape(-1, 64)
+    s = to_dev(x)
+    out = torch.empty((len(cases), 6, 64), dtype=torch.int64, device="cuda")
+    for k, (name, dx, dy) in enumerate(cases):
+        hip.symmetricize(s, name, dx, dy, out=out[k])
+    assert first_difference(to_host(out), want, cases) is None
+    assert (to_host(s) == x).all()
+
+
+def test_bounds_and_orbit_extreme_pairs(hip, sweeps):
+    """every pair of populated columns and every pair of populated rows: the
+    bounds and the masks against the recording, the images (two cells each)
+    against the model; and the first 8191 from a buffer that is only 8-byte
+    aligned"""
+    x = M.pair_states()
+    want_images, want_mask = M.np_orbit_batch(x)
+    assert (want_mask == sweeps["pair_mask"]).all()
+    for n, offset8 in ((8192, False), (8191, True)):
+        s = to_dev(x[:n], offset8)
+        assert (to_host(hip.bounds(s)).view(np.int32) == sweeps["pair_bounds"][:n]).all(), offset8
+        images, mask = hip.symmetry_orbit(s)
+        assert (mask.cpu().numpy() == sweeps["pair_mask"][:n]).all(), offset8
+        assert (to_host(images) == want_images[:n]).all(), offset8
+        assert (hip.symmetry_orbit(s, images=False).cpu().numpy() == sweeps["pair_mask"][:n]).all(), offset8
+        assert (to_host(s) == x[:n]).all()
+
+
+def test_orbit_every_stabiliser(hip, sweeps):
+    """a state for each of the 10 stabiliser subgroups at three places, the 9
+    symmetricized patterns, and the two frames whose images differ in one half
+    only, against the recording; then each of them at either place of a wave's
+    two universes, next to the empty state"""
+    x = M.orbit_sweep_states()
+    n = len(x)
+    for order in ("once", "paired"):
+        if order == "once":
+            at = np.arange(n)
+            batch = x
+        else:   # s, empty, empty, s
+            at = 4 * np.arange(n)
+            batch = np.zeros((4 * n, 64), np.uint64)
+            batch[at] = batch[at + 3] = x
+        s = to_dev(batch)
+        images, mask = hip.symmetry_orbit(s)
+        images, mask = to_host(images), mask.cpu().numpy()
+        only = hip.symmetry_orbit(s, images=False).cpu().numpy()
+        bounds = to_host(hip.bounds(s)).view(np.int32)
+        for k in ((0,) if order == "once" else (0, 3)):
+            assert (mask[at + k] == sweeps["orbit_mask"]).all(), (order, k)
+            assert (only[at + k] == sweeps["orbit_mask"]).all(), (order, k)
+            assert (images[at + k] == sweeps["orbit_images"]).all(), (order, k)
+            assert (bounds[at + k] == sweeps["orbit_bounds"]).all(), (order, k)
+        if order == "paired":
+            for k in (1, 2):
+                assert (mask[at + k] == 1).all() and (only[at + k] == 1).all() and (images[at + k] == 0).all()
+                assert (bounds[at + k] == -1).all()
+        assert (to_host(s) == batch).all()
 
 
 # ---- the order book ---------------------------------------------------------------

@@ -10,6 +10,13 @@ permutations.  The table of maps is not taken on trust: the test derives each
 transform's A and b from the recorded images of single cells.  Every mutation
 listed at the end must contradict a recorded answer.
 
+tests/golden/symmetry_sweeps.npz (make_symmetry_golden.py --only-sweeps) holds
+the reference's answers on the sweeps built below: every residue of a shift
+for every transform, every symmetry along two lines of 141 offsets, the
+bounds and orbit masks of every pair of populated columns and of rows, a
+state for every stabiliser subgroup of D4, and two states whose images
+differ in one 32-row half only.
+
 The GPU tests (tests/test_gpu_symmetry.py) and the generator import the
 models and the inputs from here.
 """
@@ -119,8 +126,8 @@ def np_transform_batch(states, t, dx=0, dy=0):
     g = np.unpackbits(s.view(np.uint8).reshape(-1, 64, 8), axis=2, bitorder="little").reshape(-1, 64, 64)
     k = np.arange(64)
     fx, fy = (sx * (k - bx)) % 64, (sy * (k - by)) % 64   # X -> x (or y with swap), Y -> y (or x)
-    out = g[:, fy][:, :, fx].transpose(0, 2, 1) if swap else g[:, fx][:, :, fy]
-    return np.packbits(np.ascontiguousarray(out), axis=2, bitorder="little").view(np.uint64).reshape(-1, 64)
+    out = g.take(fy, axis=1).take(fx, axis=2).transpose(0, 2, 1) if swap else g.take(fx, axis=1).take(fy, axis=2)
+    return np.packbits(np.ascontiguousarray(out).reshape(-1), bitorder="little").view(np.uint64).reshape(-1, 64)
 
 
 # ---- Symmetricize ----
@@ -272,6 +279,99 @@ def gold():
     return dict(np.load(GOLDEN))
 
 
+# ---- the sweeps (tests/golden/symmetry_sweeps.npz): every residue of a shift, every symmetry at every offset
+# of two lines, the extreme pairs of a bounding box, every stabiliser subgroup, and images that differ in one
+# half only.  Inputs are built here and never stored. ----
+SWEEPS = os.path.join(os.path.dirname(GOLDEN), "symmetry_sweeps.npz")
+SWEEP_CELL = (17, 42)
+SHIFT_SWEEPS = {"dx": tuple((k, -27) for k in range(64)), "dy": tuple((13, k) for k in range(64)),
+                "both": tuple((k, k) for k in range(64))}
+SHIFT_EXTREMES = ((-1, -64), (64, 63), (-65, 129), (2 ** 31 - 1, -2 ** 31))
+SHIFTS = SHIFT_SWEEPS["dx"] + SHIFT_SWEEPS["dy"] + SHIFT_SWEEPS["both"] + SHIFT_EXTREMES
+IN_PLACE_K = (0, 16, 31, 32, 33, 63)        # of each sweep: also run in place on the GPU
+SYM_SWEEP_DX = tuple((dx, 13) for dx in range(-70, 71))
+SYM_SWEEP_DY = tuple((-40, dy) for dy in range(-70, 71))
+SYM_SWEEP = SYM_SWEEP_DX + SYM_SWEEP_DY
+# the 10 subgroups of the orbit's eight transforms, as indices into ORBIT_ORDER (0 Identity, 1 ReflectAcrossX,
+# 2 ReflectAcrossYeqX, 3 ReflectAcrossY, 4 ReflectAcrossYeqNegXP1, 5 Rotate90, 6 Rotate270, 7 Rotate180OddBoth)
+SUBGROUPS = {"1": (0,), "AcrossX": (0, 1), "YeqX": (0, 2), "AcrossY": (0, 3), "YeqNegX": (0, 4), "C2": (0, 7),
+             "C4": (0, 5, 6, 7), "D2axes": (0, 1, 3, 7), "D2diag": (0, 2, 4, 7), "D4": tuple(range(8))}
+STABILISER_SPOTS = ((0, 0), (-3, 40), (29, 30))   # the last straddles the window's seam
+STABILISER_MASKS = (0xFF, 0x1D, 0x1B, 0x17, 0x0F, 0x27, 0x05, 0x03, 0x01)
+FRAME_EXTRA = ((5, 35), (35, 5))            # the one cell added to the 40 x 40 frame, in frame coordinates
+
+
+def cells(points):
+    s = np.zeros(64, np.uint64)
+    for x, y in points:
+        s[x % 64] |= np.uint64(1) << np.uint64(y % 64)
+    return s
+
+
+def pair_states():
+    """{(a, 5), (b, 40)} and then {(7, a), (50, b)} for all a, b in 0..63: every
+    pair of populated columns, then of populated rows"""
+    word = np.uint64(1) << np.arange(64, dtype=np.uint64)
+    a, b = (v.ravel() for v in np.meshgrid(np.arange(64), np.arange(64), indexing="ij"))
+    s, n = np.zeros((8192, 64), np.uint64), np.arange(4096)
+    s[n, a] |= word[5]
+    s[n, b] |= word[40]
+    s[4096 + n, 7] |= word[a]
+    s[4096 + n, 50] |= word[b]
+    return s
+
+
+def stabiliser_pattern():
+    """7 seeded cells within radius 6 of the origin, at the origin"""
+    rng = np.random.default_rng(909)
+    at = rng.choice(13 * 13, size=7, replace=False)
+    return cells([(int(k) // 13 - 6, int(k) % 13 - 6) for k in at])
+
+
+def stabiliser_states():
+    """per subgroup H and spot, the union over H of the pattern's images, moved
+    to the spot; then Symmetricize(pattern, sym, 0, 0) for the 9 symmetries"""
+    p = stabiliser_pattern()
+    out = []
+    for h in SUBGROUPS.values():
+        u = np.bitwise_or.reduce([np_transform(p, ORBIT_ORDER[i]) for i in h])
+        out += [np_transform(u, 0, dx, dy) for dx, dy in STABILISER_SPOTS]
+    out += [np_symmetricize(p, sym, 0, 0) for sym in SYMMETRIES.values()]
+    return np.stack(out)
+
+
+STABILISER_NAMES = tuple(f"{h}@{spot}" for h in SUBGROUPS for spot in STABILISER_SPOTS) + tuple(SYMMETRIES)
+
+
+def frame_states():
+    """the 40 x 40 square frame at (-20, -20) and one more cell: taller and
+    wider than 32, all eight images distinct, two of them in one half only"""
+    frame = [(x - 20, y - 20) for x in range(40) for y in range(40) if x in (0, 39) or y in (0, 39)]
+    return np.stack([cells(frame + [(fx - 20, fy - 20)]) for fx, fy in FRAME_EXTRA])
+
+
+def orbit_sweep_states():
+    return np.concatenate([stabiliser_states(), frame_states()])
+
+
+def first_masks(images, keep=np.uint64(2 ** 64 - 1), columns=slice(None)):
+    """the orbit's mask from (n, 8, 64) images, compared on the rows of `keep`
+    and the given columns only"""
+    v = (np.asarray(images, np.uint64) & keep)[:, :, columns]
+    masks = np.zeros(len(v), np.uint8)
+    for i in range(8):
+        new = np.ones(len(v), bool)
+        for j in range(i):
+            new &= (v[:, j] != v[:, i]).any(axis=1)
+        masks |= new.astype(np.uint8) << np.uint8(i)
+    return masks
+
+
+@pytest.fixture(scope="module")
+def sweeps():
+    return dict(np.load(SWEEPS))
+
+
 # ---- the table is derived from the recorded impulses ----
 def where(state):
     g = unpack(state)
@@ -358,7 +458,88 @@ def test_golden_sharp_edges(gold):
     assert any(k & (k >> 1) != k >> 1 for k in masks)   # a set bit above a clear one
 
 
+# ---- the sweeps ----
+def test_shift_sweep_golden(sweeps):
+    """Transformed(t).Moved(dx, dy) of one cell at every residue of dx, of dy
+    and of both, and at moves far out of range"""
+    s = cell(*SWEEP_CELL)
+    for t in range(16):
+        for m, (dx, dy) in enumerate(SHIFTS):
+            want = cell(*sweeps["shift_landing"][t][m].tolist())
+            assert (np_transform(s, t, dx, dy) == want).all(), (TRANSFORMS[t], dx, dy)
+            assert (np_transform_batch(s[None], t, dx, dy)[0] == want).all(), (TRANSFORMS[t], dx, dy)
+    # on the recording alone: the 64 residues of a sweep land the cell on 64 places
+    for k in range(3):
+        for t in range(16):
+            assert len({tuple(c) for c in sweeps["shift_landing"][t][64 * k:64 * k + 64].tolist()}) == 64, (k, t)
+    # and a far move is its residue: (-1, -64) and (2^31 - 1, -2^31) are both (63, 0) mod 64
+    far = sweeps["shift_landing"][:, 192:]
+    assert (far[:, 0] == far[:, 3]).all() and (far[:, 0] != far[:, 1]).any(axis=1).all()
+
+
+def test_symmetricize_sweep_golden(port, sweeps):
+    s = symmetricize_states(port)[0]
+    for k, sym in enumerate(SYMMETRIES.values()):
+        for o, (dx, dy) in enumerate(SYM_SWEEP):
+            assert (np_symmetricize(s, sym, dx, dy) == sweeps["symmetricize_sweep"][k][o]).all(), (sym, dx, dy)
+            assert (np_symmetricize(s[None], sym, dx, dy)[0] == sweeps["symmetricize_sweep"][k][o]).all()
+
+
+def test_extreme_pairs_golden(sweeps):
+    pairs = pair_states()
+    bounds = np_bounds_batch(pairs)
+    assert (bounds == sweeps["pair_bounds"]).all()
+    assert (np_orbit_batch(pairs)[1] == sweeps["pair_mask"]).all()
+    for u in range(0, 8192, 97):   # and the scalar forms on a sample
+        assert np_bounds(pairs[u]) == tuple(sweeps["pair_bounds"][u]) and np_orbit(pairs[u])[1] == sweeps["pair_mask"][u]
+    # on the recording alone: most boxes of the window occur
+    assert len({tuple(b) for b in sweeps["pair_bounds"].tolist()}) >= 4000
+
+
+def test_stabilisers_and_frames_golden(sweeps):
+    states = orbit_sweep_states()
+    assert len(states) == len(STABILISER_NAMES) + 2 == len(sweeps["orbit_mask"])
+    assert (np_bounds_batch(states) == sweeps["orbit_bounds"]).all()
+    images, masks = np_orbit_batch(states)
+    assert (images == sweeps["orbit_images"]).all() and (masks == sweeps["orbit_mask"]).all()
+    for u, s in enumerate(states):
+        one, mask = np_orbit(s)
+        assert (one == sweeps["orbit_images"][u]).all() and mask == sweeps["orbit_mask"][u], u
+
+
+def test_sweeps_sharp_edges(sweeps):
+    """on the recording alone: every stabiliser subgroup's mask occurs, the two
+    subgroups that share a mask differ in their images, and the frames' images
+    differ in one half only"""
+    images, masks = sweeps["orbit_images"], sweeps["orbit_mask"]
+    stab = masks[:len(STABILISER_NAMES)]
+    assert set(STABILISER_MASKS) <= set(stab.tolist()), sorted(set(stab.tolist()))
+    c4, klein = STABILISER_NAMES.index("C4@(0, 0)"), STABILISER_NAMES.index("D2diag@(0, 0)")
+    assert masks[c4] == masks[klein] == 0x03 and (images[c4] != images[klein]).any()
+    # C4 sends the pattern's reflection to one other image, the diagonal Klein group to the pattern itself
+    assert (images[c4][1] == images[c4][2]).all() and (images[klein][0] == images[klein][2]).all()
+    assert (sweeps["orbit_bounds"][-2:] == (-20, -20, 19, 19)).all() and (masks[-2:] == 0xFF).all()
+    assert (first_masks(images) == masks).all()
+    low = np.uint64(0xFFFFFFFF)
+    assert first_masks(images[-2:], keep=low).tolist() == [0xA7, 0x5B]           # rows < 32 only
+    assert first_masks(images[-2:], keep=~low).tolist() == [0x5B, 0xA7]          # rows >= 32 only
+    assert first_masks(images[-2:], columns=slice(0, 32)).tolist() == [0x37, 0xCD]
+    assert first_masks(images[-2:], columns=slice(32, 64)).tolist() == [0xCD, 0x37]
+    tall = images[-2]
+    assert ((tall[0] ^ tall[3]) & low == 0).all() and (tall[0] != tall[3]).any()   # images 0 and 3: a row >= 32
+
+
 # ---- mutations: each must contradict a recorded answer ----
+def test_mutation_perp_component_sweep(port, sweeps):
+    """floor division, or the offset reduced mod 64 first, in PerpComponent:
+    each is contradicted on the dx sweep, where the reference truncates"""
+    s, k = symmetricize_states(port)[0], list(SYMMETRIES).index("D4diag")
+    for perp in (perp_floor, perp_mod64):
+        told = [(np_symmetricize(s, SYMMETRIES["D4diag"], dx, dy, perp=perp) != sweeps["symmetricize_sweep"][k][o]).any()
+                for o, (dx, dy) in enumerate(SYM_SWEEP_DX)]
+        assert any(told), perp.__name__
+
+
 def transform_contradicted(gold, port, **kw):
     states = transform_states(port)
     return any((np_transform(s, t, **kw) != gold["transform"][t][k]).any()
