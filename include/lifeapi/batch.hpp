@@ -526,6 +526,96 @@ std::vector<S> WeldInteractionOffsetsBatch(std::span<const W> welds, const W &ot
   return out;
 }
 
+// ---- completing still lifes ----
+//
+// LifeStable::CompletionResult (LifeStable.hpp:128-132) in the reference's
+// order, then the two results only the batched search has: a search that
+// needed more than max_depth frames, and useSeed with an empty seed.
+enum class CompletionResult : uint8_t { COMPLETED = 0, INCONSISTENT = 1, TIMEOUT = 2, TOO_DEEP = 3, BAD_SEED = 4 };
+
+template <LifeStateLayout L>
+struct Completions {
+  std::vector<CompletionResult> result;
+  std::vector<L> best;          // LifeState() unless COMPLETED
+  std::vector<uint64_t> nodes;  // entries of CompleteStableStep
+};
+
+namespace detail {
+template <LifeStableLayout S, LifeStateLayout L>
+Completions<L> complete_stable(std::span<const S> s, bool minimise, const uint64_t *seeds, int per, uint64_t node_budget,
+                               uint32_t max_depth, int device) {
+  const size_t n = s.size();
+  Completions<L> c{std::vector<CompletionResult>(n), std::vector<L>(n), std::vector<uint64_t>(n)};
+  static_assert(sizeof(CompletionResult) == 1);
+  check(lifeapi_stable_complete_batch(words(s.data()), seeds, per,
+                                      (minimise ? LIFEAPI_COMPLETE_MINIMISE : 0u) | (seeds ? LIFEAPI_COMPLETE_USE_SEED : 0u),
+                                      node_budget, max_depth, words(c.best.data()),
+                                      reinterpret_cast<uint8_t *>(c.result.data()), c.nodes.data(), n, device));
+  return c;
+}
+}  // namespace detail
+
+// s[i].CompleteStable(timeout, minimise[, true, seed]) (LifeStable.hpp:1414-1458)
+// with a per-object node budget (0 = 65536) in place of the timeout: see
+// lifeapi_stable_complete_batch_dev for where the budget is read, the quirks
+// kept and the three cases defined.  s is not changed.
+template <LifeStableLayout S, LifeStateLayout L>
+Completions<L> CompleteStableBatch(std::span<const S> s, bool minimise = false, uint64_t node_budget = 0,
+                                   uint32_t max_depth = 64) {
+  return detail::complete_stable<S, L>(s, minimise, nullptr, 0, node_budget, max_depth, 0);
+}
+// ... useSeed, one seed for the batch
+template <LifeStableLayout S, LifeStateLayout L>
+Completions<L> CompleteStableBatch(std::span<const S> s, bool minimise, uint64_t node_budget, uint32_t max_depth,
+                                   const L &seed) {
+  return detail::complete_stable<S, L>(s, minimise, words(&seed), 0, node_budget, max_depth, 0);
+}
+// ... useSeed, seeds[i] for s[i]
+template <LifeStableLayout S, LifeStateLayout L>
+Completions<L> CompleteStableBatch(std::span<const S> s, bool minimise, uint64_t node_budget, uint32_t max_depth,
+                                   std::span<const L> seeds) {
+  if (seeds.size() != s.size()) throw Error(LIFEAPI_E_INVALID, "lifeapi: size mismatch");
+  return detail::complete_stable<S, L>(s, minimise, words(seeds.data()), 1, node_budget, max_depth, 0);
+}
+
+// weld.UnweldableMask(other, startingGood, startingBad) (LifeWeld.hpp:247-277):
+// the offsets at which `other` cannot be placed next to `weld` -- those that
+// interact, startingBad, and of the rest (outside startingGood) those whose
+// placement weld | other.Moved(cell) has no stable completion.  The reference
+// gives each placement's CompleteStable 0.05 s; here it gets node_budget nodes
+// (0 = 65536).  As there, only INCONSISTENT marks a cell: a placement whose
+// search times out (or needs more than 64 frames) stays unmarked.  The
+// placements are built here, and go through WeldToStable and CompleteStable
+// as one batch of at most 4096.
+template <LifeWeldLayout W, LifeStateLayout L>
+L UnweldableMask(const W &weld, const W &other, const L &startingGood, const L &startingBad, uint64_t node_budget = 0) {
+  L bad;
+  uint64_t *kb = words(&bad);
+  check(lifeapi_weld_interaction_offsets_batch(words(&weld), words(&other), kb, 1, 0));
+  const uint64_t *good = words(&startingGood), *sb = words(&startingBad), *a = words(&weld), *b = words(&other);
+  std::vector<std::pair<unsigned, unsigned>> cells;
+  for (unsigned x = 0; x < 64; ++x) {
+    kb[x] |= sb[x];
+    for (uint64_t m = ~good[x] & ~kb[x]; m; m &= m - 1) cells.push_back({x, (unsigned)std::countr_zero(m)});
+  }
+  if (cells.empty()) return bad;
+  std::vector<W> placed(cells.size());
+  for (size_t i = 0; i < cells.size(); ++i) {
+    uint64_t *p = words(&placed[i]);
+    const auto [x, y] = cells[i];
+    for (unsigned k = 0; k < 4 * 64; ++k)  // weld | other.Moved(cell), plane by plane
+      p[(k & ~63u) | ((k + x) & 63u)] = a[(k & ~63u) | ((k + x) & 63u)] | std::rotl(b[k], (int)y);
+  }
+  struct alignas(64) Stable {
+    uint64_t planes[10 * 64];
+  };
+  const std::vector<Stable> stables = WeldToStableBatch<Stable, W>(std::span<const W>(placed));
+  const Completions<L> c = CompleteStableBatch<Stable, L>(std::span<const Stable>(stables), false, node_budget, 64);
+  for (size_t i = 0; i < cells.size(); ++i)
+    if (c.result[i] == CompletionResult::INCONSISTENT) kb[cells[i].first] |= 1ull << cells[i].second;
+  return bad;
+}
+
 // The search-loop idiom over a batch, in place (LifeAPI.hpp:1196-1216,
 // LifeTarget.hpp:44-51):
 //     for (unsigned g = 1; g <= gens; ++g) { s.Step(); if (!first && s.Contains(target)) first = g; }

@@ -313,6 +313,67 @@ int lifeapi_stable_test_unknowns_batch_dev(uint64_t *d_planes, const uint64_t *d
  * stops any, d_flags[u] = 4 and object u is not written at all.             */
 int lifeapi_stable_propagate_and_test_batch_dev(uint64_t *d_planes, uint8_t *d_flags, size_t n,
                                                 uint32_t max_iters, void *stream);
+/* d_planes[u].CompleteStable(minimise, useSeed, seed) (LifeStable.hpp:
+ * 1340-1458): given the known part of a still life, find the rest, or prove
+ * that there is none.  A backtracking search, one wave per object, its
+ * recursion an explicit stack of frames in d_workspace.
+ *
+ * The reference's wall-clock timeout is a per-object node budget.  `nodes`
+ * counts the entries of CompleteStableStep over the whole call, tail calls
+ * (the on-branches) included, and "the clock is past the limit" is
+ * nodes >= node_budget, tested where the reference reads the time: at the
+ * entry of CompleteStableStep (:1343), before the node counts itself, so that
+ * exactly node_budget nodes can run; and after each search-area round (:1439).
+ * node_budget 0 = 1 << 16; above 1 << 24 is LIFEAPI_E_INVALID (one wave's
+ * search must end).
+ *
+ * Everything else is the reference's, quirks included: maxPop and best carry
+ * over between the rounds and into the minimise pass; a TIMEOUT with a
+ * non-empty best is COMPLETED (:1444); a timeout inside the minimise pass is
+ * ignored (:1450-1455); an empty state completes to the empty state and an
+ * empty unknown to the state itself, searching nothing (:1415-1420); each round
+ * masks the `unknown` plane alone; the branching cell is FirstOn of
+ * Vulnerable() & settable, else of the settable cells whose NeighbourCount of
+ * unknown is 2, else 3, else of settable (:1378-1391), FirstOn in the
+ * reference's own order (the last populated group of four columns); the
+ * pruning is currentPop >= maxPop (:1353).
+ *
+ * Three cases the reference leaves undefined are defined here:
+ *   - unknown within state.ZOI() at the start (no round would run, :1432, and
+ *     `result` be read uninitialised): CompleteStableStep runs once on the
+ *     object as given, its unknown plane unmasked, and the call goes on from
+ *     that result (searchArea = state.ZOI() for the minimise pass);
+ *   - LIFEAPI_COMPLETE_USE_SEED with an empty seed (the loop at :1369 would
+ *     not end): result 4, best empty, nothing searched -- after the two early
+ *     returns above, which do not look at the seed;
+ *   - a search that needs more than max_depth frames: result 3, best empty.
+ *
+ * d_result[u]: 0 COMPLETED, 1 INCONSISTENT, 2 TIMEOUT (the reference's enum
+ * order), 3 too deep, 4 bad seed.  d_best[u]: the completion, the empty state
+ * unless COMPLETED.  d_nodes (may be NULL): the nodes entered.  d_planes is
+ * not written.  d_seeds: one LifeState (per_object_seeds 0) or n; ignored
+ * without LIFEAPI_COMPLETE_USE_SEED.
+ *
+ * d_workspace (128-byte aligned) holds a 256-byte header and one stack of
+ * max_depth frames of 5376 bytes (the 10 planes and the cell) per resident
+ * wave, not per object: the waves claim their objects from a counter in the
+ * header.  lifeapi_stable_complete_workspace_bytes(n, max_depth) is what a
+ * full grid for n objects uses on the current device (0, with
+ * lifeapi_last_error(), if there is none or max_depth is invalid); any size
+ * that holds the header and one stack is accepted and only lowers the number
+ * of concurrent searches.  The call clears the header on `stream`.
+ *
+ * LIFEAPI_E_INVALID: null or misaligned pointers, outputs overlapping inputs,
+ * each other or the workspace, a workspace below one stack, unknown flag
+ * bits, USE_SEED with a null seed, max_depth 0 or above 4096, a budget above
+ * 1 << 24.  n == 0 succeeds with any pointers.                              */
+#define LIFEAPI_COMPLETE_MINIMISE 1u
+#define LIFEAPI_COMPLETE_USE_SEED 2u
+size_t lifeapi_stable_complete_workspace_bytes(size_t n, uint32_t max_depth);
+int lifeapi_stable_complete_batch_dev(const uint64_t *d_planes, const uint64_t *d_seeds, int per_object_seeds,
+                                      uint32_t flags, uint64_t node_budget, uint32_t max_depth, uint64_t *d_best,
+                                      uint8_t *d_result, uint64_t *d_nodes, size_t n, void *d_workspace,
+                                      size_t workspace_bytes, void *stream);
 /* LifeWeld::Step() (LifeWeld.hpp:169-186) `generations` times, in place on
  * LifeWeld[n] = {state, frozen2, frozen1, frozen0} x 64 words (the struct's
  * member order, LifeWeld.hpp:18-20); only the state planes change.        */
@@ -448,6 +509,12 @@ int lifeapi_stable_test_unknowns_batch(uint64_t *planes, const uint64_t *cells, 
                                        uint8_t *flags, size_t n, uint32_t max_iters, int device);
 int lifeapi_stable_propagate_and_test_batch(uint64_t *planes, uint8_t *flags, size_t n, uint32_t max_iters,
                                             int device);
+/* host form of lifeapi_stable_complete_batch_dev: the same arguments and
+ * checks on host arrays; it allocates its own workspace (at most 1 GiB per
+ * staging stream, kept for the process)                                     */
+int lifeapi_stable_complete_batch(const uint64_t *planes, const uint64_t *seeds, int per_object_seeds, uint32_t flags,
+                                  uint64_t node_budget, uint32_t max_depth, uint64_t *best, uint8_t *result,
+                                  uint64_t *nodes, size_t n, int device);
 /* host form of lifeapi_step_contains_batch_dev: the search-loop idiom
  * "for g in 1..gens: s.Step(); if (s.Contains(target)) ..." (LifeAPI.hpp:
  * 1196-1216, LifeTarget.hpp:44-51) over n host universes; final (may be NULL,

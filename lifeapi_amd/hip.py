@@ -105,6 +105,10 @@ _SIGS = {
     "lifeapi_stable_strip_pass_batch": ([_vp, _vp, _vp, _sz, _int, _u32, _int], _int),
     "lifeapi_stable_test_unknowns_batch": ([_vp, _vp, _int, _vp, _sz, _u32, _int], _int),
     "lifeapi_stable_propagate_and_test_batch": ([_vp, _vp, _sz, _u32, _int], _int),
+    "lifeapi_stable_complete_workspace_bytes": ([_sz, _u32], _sz),
+    "lifeapi_stable_complete_batch_dev": ([_vp, _vp, _int, _u32, ctypes.c_uint64, _u32, _vp, _vp, _vp, _sz, _vp, _sz,
+                                           _vp], _int),
+    "lifeapi_stable_complete_batch": ([_vp, _vp, _int, _u32, ctypes.c_uint64, _u32, _vp, _vp, _vp, _sz, _int], _int),
 }
 for _name, (_args, _res) in _SIGS.items():
     _f = getattr(lib, _name)
@@ -842,6 +846,72 @@ def stable_propagate_and_test_host(planes: np.ndarray, max_iters: int = 0,
     out, flags = src.reshape(n, 10 * N).copy(), np.empty(n, dtype=np.uint8)
     _check(lib.lifeapi_stable_propagate_and_test_batch(out.ctypes.data, flags.ctypes.data, n, max_iters, device))
     return out, flags
+
+
+COMPLETE_MINIMISE, COMPLETE_USE_SEED = 1, 2
+COMPLETION_RESULTS = ("completed", "inconsistent", "timeout", "too_deep", "bad_seed")
+# what stable_complete allocates at most when it is given no workspace
+COMPLETE_WORKSPACE_CAP = 1 << 30
+
+
+def stable_complete_workspace_bytes(n: int, max_depth: int = 64) -> int:
+    """Bytes of workspace a full grid of ``stable_complete`` searches uses for
+    ``n`` objects on the current device (one stack of ``max_depth`` frames per
+    resident wave); any size holding one stack is accepted."""
+    b = lib.lifeapi_stable_complete_workspace_bytes(n, max_depth)
+    if b == 0:
+        raise LifeApiError(-1, lib.lifeapi_last_error().decode(errors="replace"))
+    return b
+
+
+def stable_complete(planes: torch.Tensor, *, minimise: bool = False, seed: torch.Tensor | None = None,
+                    node_budget: int = 0, max_depth: int = 64, workspace: torch.Tensor | None = None,
+                    stream=None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``CompleteStable(minimise, seed is not None, seed)`` (LifeStable.hpp:
+    1340-1458) of (n, 10*64) planes, which are not written, with a per-object
+    node budget (0 = 65536) in place of the reference's clock: (result uint8,
+    best (n, 64), nodes int64).  result: 0 completed, 1 inconsistent, 2
+    timeout, 3 more than ``max_depth`` frames, 4 empty seed; best is empty
+    unless completed.  ``seed``: one universe or one per object.  ``workspace``:
+    a device tensor of at least one stack (``stable_complete_workspace_bytes(1,
+    max_depth)``), 128-byte aligned; None allocates one (at most 1 GiB)."""
+    n = _planes(planes, 10, "planes")
+    per = 0 if seed is None else _one_or_n(seed, n, "seed")
+    flags = (COMPLETE_MINIMISE if minimise else 0) | (COMPLETE_USE_SEED if seed is not None else 0)
+    result = torch.empty(n, dtype=torch.uint8, device=planes.device)
+    best = torch.empty((n, N), dtype=torch.int64, device=planes.device)
+    nodes = torch.empty(n, dtype=torch.int64, device=planes.device)
+    if n == 0:
+        return result, best, nodes
+    if workspace is None:
+        with torch.cuda.device(planes.device):
+            want = min(stable_complete_workspace_bytes(n, max_depth),
+                       max(COMPLETE_WORKSPACE_CAP, stable_complete_workspace_bytes(1, max_depth)))
+        workspace = torch.empty(want, dtype=torch.uint8, device=planes.device)
+    elif not workspace.is_cuda or not workspace.is_contiguous():
+        raise ValueError("workspace must be a contiguous device tensor")
+    _check(lib.lifeapi_stable_complete_batch_dev(planes.data_ptr(), None if seed is None else seed.data_ptr(), per,
+                                                 flags, node_budget, max_depth, best.data_ptr(), result.data_ptr(),
+                                                 nodes.data_ptr(), n, workspace.data_ptr(),
+                                                 workspace.numel() * workspace.element_size(), _stream(stream)))
+    return result, best, nodes
+
+
+def stable_complete_host(planes: np.ndarray, *, minimise: bool = False, seed: np.ndarray | None = None,
+                         node_budget: int = 0, max_depth: int = 64,
+                         device: int = 0) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Host-pointer ``lifeapi_stable_complete_batch``: (result, best, nodes)."""
+    src, n = _host_planes(planes, 10, "planes")
+    sd = None if seed is None else _host_u64(seed)
+    if sd is not None and sd.size // N not in (1, n):
+        raise ValueError("seed must hold one universe or one per object")
+    flags = (COMPLETE_MINIMISE if minimise else 0) | (COMPLETE_USE_SEED if sd is not None else 0)
+    result, best, nodes = np.empty(n, np.uint8), np.empty((n, N), np.uint64), np.empty(n, np.uint64)
+    _check(lib.lifeapi_stable_complete_batch(src.ctypes.data, None if sd is None else sd.ctypes.data,
+                                             int(sd is not None and sd.size // N == n and n != 1), flags, node_budget,
+                                             max_depth, best.ctypes.data, result.ctypes.data, nodes.ctypes.data, n,
+                                             device))
+    return result, best, nodes
 
 
 def neighbour_count(states: torch.Tensor, stream=None) -> torch.Tensor:
