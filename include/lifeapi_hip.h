@@ -106,11 +106,11 @@ const char *lifeapi_step_kernel_name(uint32_t generations);
 /* ---- device-resident, stream-ordered (the hot path) -------------------- */
 
 /* out[u] = in[u] stepped `generations` times (0 = copy), for u < n.  For
- * 1-2 generations and 192K <= n <= 4M a call whose input is a batch an
+ * 1-2 generations and n >= 192K a call whose input is a batch an
  * earlier call wrote walks it in the opposite order to that call (a per-device
  * book of the last batches written; a cache-locality choice for back-to-back
- * calls on the batch just written); above 4M each XCD takes a contiguous
- * eighth of the batch.  Results never depend on either, and
+ * calls on the batch just written); from 512K up to 2M and from 4M on each
+ * XCD takes a contiguous eighth of the batch.  Results never depend on either, and
  * calls from several threads are safe.                                    */
 int lifeapi_step_batch_dev(const uint64_t *d_in, uint64_t *d_out, size_t n,
                            uint32_t generations, void *stream);

@@ -14,6 +14,7 @@
 #include <cstdint>
 
 #include "common.hpp"
+#include "step_order.hpp"
 
 namespace lifeapi_impl {
 
@@ -314,10 +315,8 @@ __device__ __forceinline__ int last_set(uint64_t m) { return m ? 63 - __builtin_
 // that gives XCD x one contiguous eighth: +5-11 % on the in-place LifeStable
 // passes and +2-4 % on 8M-16M-universe steps (tools/ab/stable_xcd_ab.py,
 // tools/ab/step_xcd_ab.py).
-__device__ __forceinline__ uint64_t xcd_chunk_block() {
-  const uint32_t b = blockIdx.x, nb = gridDim.x, q = nb >> 3, r = nb & 7u, x = b & 7u;
-  return (uint64_t)x * q + (x < r ? x : r) + (b >> 3);
-}
+// (The arithmetic is step_order.hpp xcd_chunk_place, shared with the host.)
+__device__ __forceinline__ uint64_t xcd_chunk_block() { return xcd_chunk_place(blockIdx.x, gridDim.x); }
 template <bool CHUNK>
 __device__ __forceinline__ uint64_t block_index() {
   if constexpr (CHUNK) return xcd_chunk_block();

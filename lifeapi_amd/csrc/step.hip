@@ -63,10 +63,38 @@ using StepFn = void (*)(const uint64_t *, uint64_t *, uint64_t, uint32_t, uint64
 // written last; the groups that store the last min(256 MiB, half
 // the batch) of a launch use plain stores, which leave that part in the 256 MB
 // memory-side Infinity Cache, and the rest nontemporal ones, which do not
-// evict it.
-constexpr uint64_t kCachedUniverses = 1ull << 22;
+// evict it.  ("Last" is by dispatch position: under XCD chunks the end of
+// every XCD's eighth, round 17 below.)
+//
+// Round 17: the two together (tools/step_chunk_ab.py, round 7's method and
+// rule; profiles/r17/step_chunk_ab/*.jsonl, profiles/r17/README.md).  The
+// plain-stored tail is now decided by dispatch position (step_order.hpp
+// step_take), so with kXcdChunk it is the end of every XCD's eighth, which is
+// what a chunked launch writes last, and the reversed launch that follows
+// starts on those ends.  Chunks x order x tail x resident blocks x universes
+// per wave at every size, against the launch shipped until then (ms, median of
+// 7 rounds; gain over that launch's p10-p90 spread in brackets):
+// * 512K: chunks, alternating, half the batch plain, 7 blocks: 0.0740 against
+//   0.0756 (8.9 x); without chunks 7 blocks gain 0.9 % (4.0 x);
+// * 1M: chunks, alternating, 256 MiB, 7 blocks: 0.1437 against 0.1459 (10.8 x);
+// * 2M: nothing passed; the best chunked launch (alternating, 256 MiB, 6
+//   blocks) is 2.0 % slower, so 2M up to 4M keeps the plain block mapping;
+// * 4M: chunks, alternating, 256 MiB, 6 blocks: 0.6403 against 0.6575 (8.6 x),
+//   on a second box 0.6363 against 0.6576 (9.2 x); a third ran the former
+//   launch at 0.6359 and this one at 0.6410, inside the former's own range;
+// * 8M: the same: 1.2934 against 1.3181 (10.6 x); * 16M: 2.6125 against 2.6341
+//   (8.7 x).  Above 4M a fixed order with the tail gains a third of that, the
+//   alternating order without a tail nothing: it is the reuse.
+// 4 universes per wave everywhere; between two measured sizes the smaller
+// one's setting.
+constexpr uint64_t kChunkMinUniverses = 1ull << 19;   // XCD chunks from here ...
+constexpr uint64_t kChunkStopUniverses = 1ull << 21;  // ... up to here (excluded),
+constexpr uint64_t kChunkBigUniverses = 1ull << 22;   // and from here on
+bool stream_chunks(uint64_t n) {
+  return (n >= kChunkMinUniverses && n < kChunkStopUniverses) || n >= kChunkBigUniverses;
+}
 // resident blocks per CU of the streaming step (0 = as many as fit, 8)
-constexpr uint64_t kCap7Universes = 1ull << 20;  // 7 from here
+constexpr uint64_t kCap7Universes = 1ull << 19;  // 7 from here (round 17; 1M before)
 constexpr uint64_t kCap6Universes = 1ull << 21;  // 6 from here
 constexpr int kStreamResidentBlocks = 6;
 int stream_resident_blocks(uint64_t n) {
@@ -81,16 +109,14 @@ int stream_resident_blocks(uint64_t n) {
 constexpr uint64_t kOrderMinUniverses = 3ull << 16;
 constexpr uint64_t kPlainBytes = 256ull << 20;
 constexpr uint64_t kFilterOrderUniverses = 1ull << 21;  // the same for the 1-2 generation search filter
+// Two names: the launches up to kChunkBigUniverses (with it: some chunked, some
+// not) and the ones above, all chunked (kXcdChunk, device.hpp xcd_chunk_block).
 constexpr const char *kStreamName =
     "k_step<dpp, 4 universes/wave, nt loads, 7-LUT network; alternating order, the last min(256 MiB, half) of "
-    "each launch stored plain, the rest nt>";
-// Above kCachedUniverses there is no Infinity Cache reuse to arrange: one
-// order, every store nontemporal, and each XCD streams a contiguous eighth
-// of the batch (kXcdChunk, device.hpp xcd_chunk_block; round 3,
-// profiles/r03/step_xcd_ab.jsonl: 16M 2.736 ms against 2.845 with the plain
-// block mapping at 7 blocks of 8 universes per wave).
+    "each launch stored plain, the rest nt; each XCD a contiguous eighth from 512K up to 2M and from 4M universes>";
 constexpr const char *kStreamBigName =
-    "k_step<dpp, 4 universes/wave, nt, 7-LUT network; each XCD a contiguous eighth, one order>";
+    "k_step<dpp, 4 universes/wave, nt loads, 7-LUT network; each XCD a contiguous eighth, the order reversed from "
+    "launch to launch, the last 32 MiB of every eighth stored plain, the rest nt>";
 struct StepLaunch {
   StepFn fn;
   uint64_t universes_per_wave;
@@ -101,11 +127,10 @@ struct StepLaunch {
   uint32_t flags;        // kXcdChunk or 0
 };
 StepLaunch shipped_step(uint32_t gens, uint64_t n) {
-  if (gens <= 2 && n > kCachedUniverses)
-    return {k_step<XDPP, 4, true, 3, true, true>, 4, stream_resident_blocks(n), false, 0, kStreamBigName, kXcdChunk};
   if (gens <= 2)
     return {k_step<XDPP, 4, true, 3, true, true>, 4, stream_resident_blocks(n), true,
-            std::min<uint64_t>(kPlainBytes, n * 512 / 2), kStreamName, 0u};
+            std::min<uint64_t>(kPlainBytes, n * 512 / 2), n > kChunkBigUniverses ? kStreamBigName : kStreamName,
+            stream_chunks(n) ? kXcdChunk : 0u};
   if (gens < 32)
     return {k_step_split<8, 1, true, 6, kAsmLoop>, 4, 0, false, 0,
             "k_step_split<8-way split, 4 universes/wave, nt, 6-LUT tail, assembly loop>", 0u};

@@ -11,6 +11,7 @@
 #include "life_gen.hpp"
 #include "split_layout.hpp"
 #include "split_asm.inc"
+#include "step_order.hpp"
 
 namespace lifeapi_impl {
 // internal linkage: every library that includes this header gets its own
@@ -24,19 +25,24 @@ namespace {
 // wave touches another's (the same holds for k_step_split).
 // Bit 31 of `gens` (kReverse) reverses the order in which waves take the
 // groups: alternated between launches, each launch first reads what the one
-// before it wrote last.  The groups taken from position `plain_from` on (in
-// the launch's order) store with plain stores, the rest as NTS says: the
-// last-written part then stays in the memory-side Infinity Cache for the next
-// launch to read first, and the nontemporal rest does not evict it
-// (DESIGN.md 3.1).  The launcher sets both only for gens <= 2.
+// before it wrote last.  The waves from dispatch position `plain_from` on
+// (block x waves per block + wave, the order in which the grid is dispatched)
+// store with plain stores, the rest as NTS says: the last-written part then
+// stays in the memory-side Infinity Cache for the next launch to read first,
+// and the nontemporal rest does not evict it.  The launcher
+// sets both only for gens <= 2.
 constexpr uint32_t kReverse = 1u << 31;
 // Bit 30 of `gens` (kXcdChunk): each XCD takes a contiguous eighth of the
-// groups (xcd_chunk_block); the launcher sets it for large batches.
+// groups (xcd_chunk_block); the plain-stored tail is then the end of every
+// XCD's eighth, and a reversed launch starts on those ends.
 constexpr uint32_t kXcdChunk = 1u << 30;
-// (The decode of these two bits is written out in step_body, step_body_dma
-// and contains_kernels.hpp k_step_contains, and the store tail below in
-// k_step_contains too: through shared helpers the kernels compile to other
-// code, tools/isa_diff.py and profiles/r08/README.md.)
+// step_body takes all of this from step_order.hpp step_take, which a host
+// test checks wave by wave (tests/test_step_chunk_order.py).  (The decode of
+// the two bits is written out in step_body_dma and contains_kernels.hpp
+// k_step_contains, and the store tail in k_step_contains too, by group index
+// as before: through shared helpers those kernels compiled to other code,
+// tools/isa_diff.py and profiles/r08/README.md; k_step's difference under
+// step_take is in profiles/r17/README.md.)
 
 // NTS: nontemporal stores (default: as the loads) before `plain_from`.
 //
@@ -93,21 +99,25 @@ __device__ __forceinline__ void step_body(const uint64_t *in, uint64_t *out, uin
   // wave index in the block, made provably wave-uniform so that the tail
   // tests below are scalar branches
   const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
-  const bool rev = (gens & kReverse) != 0;
-  const uint64_t blk = (gens & kXcdChunk) ? xcd_chunk_block() : (uint64_t)blockIdx.x;
+  const bool rev = (gens & kReverse) != 0, chunk = (gens & kXcdChunk) != 0;
   gens &= ~(kReverse | kXcdChunk);
-  const uint64_t groups = (n + U - 1) / U, wstride = (uint64_t)gridDim.x * kWavesPerBlock;
+  const uint64_t groups = (n + U - 1) / U;
   uint64_t *slot = lds + (uses_lds(X) ? wib * U * 2 * kWave : 0);
-  auto group = [&](uint64_t grp) __attribute__((always_inline)) {
-    const uint64_t u0 = (rev ? groups - 1 - grp : grp) * U;
-    if (u0 + U <= n) step_group<X, U, NT, RULE, NTS, true>(in, out, n, gens, u0, grp < plain_from, slot, lane);
-    else step_group<X, U, NT, RULE, NTS, false>(in, out, n, gens, u0, grp < plain_from, slot, lane);
+  // the wave's pass-th group: its index in the launch's order, the group, and
+  // whether it stores plain (by dispatch position: step_order.hpp step_take)
+  auto take = [&](uint64_t pass) __attribute__((always_inline)) {
+    const StepTake t = step_take(blockIdx.x, gridDim.x, wib, pass, groups, chunk, rev, plain_from);
+    if (t.index >= groups) return false;
+    const uint64_t u0 = t.group * U;
+    if (u0 + U <= n) step_group<X, U, NT, RULE, NTS, true>(in, out, n, gens, u0, !t.plain, slot, lane);
+    else step_group<X, U, NT, RULE, NTS, false>(in, out, n, gens, u0, !t.plain, slot, lane);
+    return true;
   };
-  const uint64_t first = blk * kWavesPerBlock + wib;
   if constexpr (ONESHOT) {
-    if (first < groups) group(first);
+    take(0);
   } else {
-    for (uint64_t grp = first; grp < groups; grp += wstride) group(grp);
+    for (uint64_t pass = 0; take(pass); ++pass) {
+    }
   }
 }
 
@@ -130,8 +140,9 @@ __global__ __launch_bounds__(kBlock) void k_step_ab(const uint64_t *in, uint64_t
 // sixteen-byte-per-lane global_load_lds in (lanes 0-31 one universe, 32-63 the
 // next), ds_read_b64 out to lane = column; WIDE: the results back through the
 // image, 16 bytes per lane (ds_write_b64, ds_read_b128, global_store_dwordx4),
-// else 8-byte stores from the lanes.  Order, plain-stored tail and XCD
-// chunking as step_body.  The batch must be 16-byte aligned.
+// else 8-byte stores from the lanes.  Order and XCD chunking as step_body;
+// the plain-stored tail by group index (with chunks: not the part written
+// last).  The batch must be 16-byte aligned.
 template <int U, int RULE, bool NTS, bool WIDE>
 __device__ __forceinline__ void step_body_dma(const uint64_t *in, uint64_t *out, uint64_t n, uint32_t gens,
                                               uint64_t plain_from) {
