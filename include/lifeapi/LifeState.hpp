@@ -317,6 +317,45 @@ struct alignas(64) LifeState {
       }
     return r;
   }
+  // ---- doubled coordinates to offsets (Symmetry.hpp:681-727), CPU, single
+  // universe; batches go to the GPU via lifeapi::HalveBatch / SkewBatch.
+  // Halve: cell (2x, 2y) -> (x, y), the 32 x 32 result repeated in all four
+  // quarters; HalveX / HalveY halve one axis.  Cells at odd coordinates vanish.
+  static uint64_t EvenRows(uint64_t v) {  // bit 2y -> bit y, then the 32 bits twice
+    v &= 0x5555555555555555ULL;
+    v = (v | v >> 1) & 0x3333333333333333ULL;
+    v = (v | v >> 2) & 0x0F0F0F0F0F0F0F0FULL;
+    v = (v | v >> 4) & 0x00FF00FF00FF00FFULL;
+    v = (v | v >> 8) & 0x0000FFFF0000FFFFULL;
+    v = (v | v >> 16) & 0x00000000FFFFFFFFULL;
+    return v | v << 32;
+  }
+  LifeState Halve() const {
+    LifeState r(InitializedTag::UNINITIALIZED);
+    for (int i = 0; i < N / 2; ++i) r.state[i] = r.state[i + N / 2] = EvenRows(state[2 * i]);
+    return r;
+  }
+  LifeState HalveX() const {
+    LifeState r(InitializedTag::UNINITIALIZED);
+    for (int i = 0; i < N / 2; ++i) r.state[i] = r.state[i + N / 2] = state[2 * i];
+    return r;
+  }
+  LifeState HalveY() const {
+    LifeState r(InitializedTag::UNINITIALIZED);
+    for (int i = 0; i < N; ++i) r.state[i] = EvenRows(state[i]);
+    return r;
+  }
+  // Skew: (x, y) -> (x, y + x); InvSkew: (x, y) -> (x, y - x)
+  LifeState Skew() const {
+    LifeState r(InitializedTag::UNINITIALIZED);
+    for (int i = 0; i < N; ++i) r.state[i] = std::rotl(state[i], i);
+    return r;
+  }
+  LifeState InvSkew() const {
+    LifeState r(InitializedTag::UNINITIALIZED);
+    for (int i = 0; i < N; ++i) r.state[i] = std::rotr(state[i], i);
+    return r;
+  }
   // ---- connected components, CPU, single universe; batches go to the GPU
   // via lifeapi::FirstOn / ComponentContaining / ComponentCounts / Components.
   // FirstOn (LifeAPI.hpp:301-323): the LAST group of four columns that is not
@@ -636,6 +675,27 @@ inline LifeState Symmetricize(const LifeState &state, StaticSymmetry sym, std::p
   }
   default: __builtin_unreachable();
   }
+}
+
+// Symmetry.hpp:729-768: the offsets at which the image of pat1 under the
+// symmetry touches pat2, pat2.Convolve(pat1.Transformed(t)).  Defined for the
+// six symmetries below, as in the reference.  CPU, single pair; batches go to
+// the GPU via lifeapi::IntersectingOffsetsBatch.
+inline LifeState IntersectingOffsets(const LifeState &pat1, const LifeState &pat2, StaticSymmetry sym) {
+  using enum SymmetryTransform;
+  switch (sym) {
+  case StaticSymmetry::C2: return pat2.Convolve(pat1);
+  case StaticSymmetry::C4: return pat2.Convolve(pat1.Transformed(Rotate270));
+  case StaticSymmetry::D2AcrossX: return pat2.Convolve(pat1.Transformed(ReflectAcrossY));
+  case StaticSymmetry::D2AcrossY: return pat2.Convolve(pat1.Transformed(ReflectAcrossX));
+  case StaticSymmetry::D2diagodd: return pat2.Convolve(pat1.Transformed(ReflectAcrossYeqNegXP1));
+  case StaticSymmetry::D2negdiagodd: return pat2.Convolve(pat1.Transformed(ReflectAcrossYeqX));
+  default: __builtin_unreachable();
+  }
+}
+// Symmetry.hpp:770-772
+inline LifeState IntersectingOffsets(const LifeState &active, StaticSymmetry sym) {
+  return IntersectingOffsets(active, active, sym);
 }
 
 // LifeTarget.hpp:5-36 (the search-loop subset)

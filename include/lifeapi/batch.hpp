@@ -326,6 +326,70 @@ void SymmetricizeBatch(std::span<const S> in, std::span<S> out, Y sym, std::pair
   check(lifeapi_symmetricize_batch(words(in.data()), words(out.data()), in.size(), static_cast<uint32_t>(sym),
                                    offset.first, offset.second, device));
 }
+// ---- a symmetric search's step with everything per universe: the offsets at
+// which the symmetric image would touch the active region, then the state
+// symmetricized at the offset chosen for it ----
+namespace detail {
+inline std::vector<int32_t> offset_words(std::span<const std::pair<int, int>> offsets, size_t n) {
+  if (offsets.size() != n) throw Error(LIFEAPI_E_INVALID, "lifeapi: size mismatch");
+  std::vector<int32_t> w(2 * n);
+  for (size_t i = 0; i < n; ++i) w[2 * i] = offsets[i].first, w[2 * i + 1] = offsets[i].second;
+  return w;
+}
+}  // namespace detail
+// out[i] = in[i].Transformed(t).Moved(offsets[i])  (Symmetry.hpp:105-173,
+// LifeAPI.hpp:682-735); out may be in
+template <LifeStateLayout S, class T>
+void TransformBatch(std::span<const S> in, std::span<S> out, T t, std::span<const std::pair<int, int>> offsets,
+                    int device = 0) {
+  if (out.size() != in.size()) throw Error(LIFEAPI_E_INVALID, "lifeapi: size mismatch");
+  const std::vector<int32_t> w = detail::offset_words(offsets, in.size());
+  check(lifeapi_transform_offsets_batch(words(in.data()), words(out.data()), in.size(), static_cast<uint32_t>(t),
+                                        w.data(), device));
+}
+// out[i] = Symmetricize(in[i], sym, offsets[i])  (Symmetry.hpp:565-654); out may be in
+template <LifeStateLayout S, class Y>
+void SymmetricizeBatch(std::span<const S> in, std::span<S> out, Y sym, std::span<const std::pair<int, int>> offsets,
+                       int device = 0) {
+  if (out.size() != in.size()) throw Error(LIFEAPI_E_INVALID, "lifeapi: size mismatch");
+  const std::vector<int32_t> w = detail::offset_words(offsets, in.size());
+  check(lifeapi_symmetricize_offsets_batch(words(in.data()), words(out.data()), in.size(),
+                                           static_cast<uint32_t>(sym), w.data(), device));
+}
+// out[i] = a[i].Convolve(b[i].Transformed(t))  (LifeAPI.hpp:1293-1370): both
+// operands per universe; b may be a, out may be a or b
+template <LifeStateLayout S, class T>
+void ConvolvePairBatch(std::span<const S> a, std::span<const S> b, T t, std::span<S> out, int device = 0) {
+  if (b.size() != a.size() || out.size() != a.size()) throw Error(LIFEAPI_E_INVALID, "lifeapi: size mismatch");
+  check(lifeapi_convolve_pair_batch(words(a.data()), words(b.data()), static_cast<uint32_t>(t), words(out.data()),
+                                    a.size(), device));
+}
+// out[i] = IntersectingOffsets(pat1[i], pat2[i], sym)  (Symmetry.hpp:729-768)
+template <LifeStateLayout S, class Y>
+void IntersectingOffsetsBatch(std::span<const S> pat1, std::span<const S> pat2, Y sym, std::span<S> out,
+                              int device = 0) {
+  if (pat2.size() != pat1.size() || out.size() != pat1.size()) throw Error(LIFEAPI_E_INVALID, "lifeapi: size mismatch");
+  check(lifeapi_intersecting_offsets_batch(words(pat1.data()), words(pat2.data()), static_cast<uint32_t>(sym),
+                                           words(out.data()), pat1.size(), device));
+}
+// out[i] = IntersectingOffsets(active[i], sym)  (Symmetry.hpp:770-772)
+template <LifeStateLayout S, class Y>
+void IntersectingOffsetsBatch(std::span<const S> active, Y sym, std::span<S> out, int device = 0) {
+  IntersectingOffsetsBatch(active, active, sym, out, device);
+}
+// out[i] = in[i].Halve() / HalveX() / HalveY()  (Symmetry.hpp:681-709); out may be in
+enum class HalveMode : uint32_t { Halve = 0, HalveX = 1, HalveY = 2 };
+template <LifeStateLayout S>
+void HalveBatch(std::span<const S> in, std::span<S> out, HalveMode mode = HalveMode::Halve, int device = 0) {
+  if (out.size() != in.size()) throw Error(LIFEAPI_E_INVALID, "lifeapi: size mismatch");
+  check(lifeapi_halve_batch(words(in.data()), words(out.data()), in.size(), static_cast<uint32_t>(mode), device));
+}
+// out[i] = in[i].Skew(), or with inverse in[i].InvSkew()  (Symmetry.hpp:711-727); out may be in
+template <LifeStateLayout S>
+void SkewBatch(std::span<const S> in, std::span<S> out, bool inverse = false, int device = 0) {
+  if (out.size() != in.size()) throw Error(LIFEAPI_E_INVALID, "lifeapi: size mismatch");
+  check(lifeapi_skew_batch(words(in.data()), words(out.data()), in.size(), inverse ? 1 : 0, device));
+}
 // r[i] = in[i].XYBounds()  (LifeAPI.hpp:446-484)
 template <LifeStateLayout S>
 std::vector<std::array<int, 4>> XYBoundsBatch(std::span<const S> in, int device = 0) {

@@ -27,6 +27,14 @@
  *                                Transpose, Mirrored        LifeAPI.hpp:682-806
  *   lifeapi_symmetricize_batch[_dev] Symmetricize, PerpComponent
  *                                                           Symmetry.hpp:540-654
+ *   lifeapi_transform_offsets_batch[_dev], lifeapi_symmetricize_offsets_batch[_dev]
+ *                                the two above with an offset per universe
+ *   lifeapi_convolve_pair_batch[_dev] a.Convolve(b.Transformed(t)), both per universe
+ *   lifeapi_intersecting_offsets_batch[_dev]
+ *                                IntersectingOffsets        Symmetry.hpp:729-772
+ *   lifeapi_halve_batch[_dev]    LifeState::Halve, HalveX, HalveY
+ *                                                           Symmetry.hpp:681-709
+ *   lifeapi_skew_batch[_dev]     LifeState::Skew, InvSkew   Symmetry.hpp:711-727
  *   lifeapi_bounds_batch[_dev]   LifeState::XYBounds        LifeAPI.hpp:446-484
  *   lifeapi_symmetry_orbit_batch[_dev]
  *                                LifeState::SymmetryOrbit, SymmetryOrbitRepresentatives
@@ -171,6 +179,41 @@ int lifeapi_transform_batch_dev(const uint64_t *d_in, uint64_t *d_out, size_t n,
  * d_out may be d_in.                                                        */
 int lifeapi_symmetricize_batch_dev(const uint64_t *d_in, uint64_t *d_out, size_t n, uint32_t symmetry,
                                    int dx, int dy, void *stream);
+/* The two calls above with an offset per universe: d_offsets is n x {dx, dy}
+ * int32 device words, any values (Move wraps; PerpComponent, Symmetry.hpp:540-563,
+ * does not reduce mod 64), universe u taking d_offsets[2u], d_offsets[2u + 1].
+ * d_out may be d_in; d_offsets overlapping d_out is LIFEAPI_E_INVALID; the
+ * transforms and symmetries accepted are those of the calls above.          */
+int lifeapi_transform_offsets_batch_dev(const uint64_t *d_in, uint64_t *d_out, size_t n,
+                                        uint32_t transform, const int32_t *d_offsets, void *stream);
+int lifeapi_symmetricize_offsets_batch_dev(const uint64_t *d_in, uint64_t *d_out, size_t n,
+                                           uint32_t symmetry, const int32_t *d_offsets, void *stream);
+/* d_out[u] = d_a[u].Convolve(d_b[u].Transformed(transform)) (LifeAPI.hpp:1293-1370,
+ * Symmetry.hpp:105-173): both operands per universe, one SymmetryTransform
+ * (0..15) per launch.  Convolve is symmetric in its operands; each universe's
+ * sparser operand is walked, so the time is proportional to the smaller
+ * population, and an empty operand gives the empty state.  d_b == d_a is the
+ * self-convolution (each universe is read once); d_out may be d_a or d_b; any
+ * other overlap is LIFEAPI_E_INVALID.                                       */
+int lifeapi_convolve_pair_batch_dev(const uint64_t *d_a, const uint64_t *d_b, uint32_t transform,
+                                    uint64_t *d_out, size_t n, void *stream);
+/* d_out[u] = IntersectingOffsets(pat1[u], pat2[u], symmetry)  (Symmetry.hpp:729-768):
+ * pat2.Convolve(pat1.Transformed(t)), t = Identity for C2, Rotate270 for C4, ReflectAcrossY for
+ * D2AcrossX, ReflectAcrossX for D2AcrossY, ReflectAcrossYeqNegXP1 for D2diagodd, ReflectAcrossYeqX
+ * for D2negdiagodd.  Every other symmetry (the reference's __builtin_unreachable, C1, D4 and
+ * D4diag included) is LIFEAPI_E_INVALID.  d_pat2 == d_pat1 is IntersectingOffsets(active, sym)
+ * (Symmetry.hpp:770-772).  Aliasing as lifeapi_convolve_pair_batch_dev.     */
+int lifeapi_intersecting_offsets_batch_dev(const uint64_t *d_pat1, const uint64_t *d_pat2,
+                                           uint32_t symmetry, uint64_t *d_out, size_t n, void *stream);
+/* d_out[u] = d_in[u].Halve() (mode 0), HalveX() (1) or HalveY() (2)
+ * (Symmetry.hpp:681-709): every second column and / or row, the half-size
+ * result repeated in both halves.  Any other mode is LIFEAPI_E_INVALID.
+ * d_out may be d_in.                                                        */
+int lifeapi_halve_batch_dev(const uint64_t *d_in, uint64_t *d_out, size_t n, uint32_t mode, void *stream);
+/* d_out[u] = d_in[u].Skew(), (x, y) -> (x, y + x) (Symmetry.hpp:711-718), or
+ * with inverse != 0 InvSkew(), (x, y) -> (x, y - x) (Symmetry.hpp:720-727).
+ * d_out may be d_in.                                                        */
+int lifeapi_skew_batch_dev(const uint64_t *d_in, uint64_t *d_out, size_t n, int inverse, void *stream);
 /* d_bounds[4u .. 4u+3] = d_states[u].XYBounds() (LifeAPI.hpp:446-484):
  * {left, top, right, bottom} in the window [-32, 31], -1 four times for an
  * empty state                                                              */
@@ -477,6 +520,18 @@ int lifeapi_transform_batch(const uint64_t *in, uint64_t *out, size_t n, uint32_
                             int device);
 int lifeapi_symmetricize_batch(const uint64_t *in, uint64_t *out, size_t n, uint32_t symmetry, int dx,
                                int dy, int device);
+/* (offsets: n x {dx, dy} int32 on the host; a, b and out of the pair calls
+ * alias as the *_dev forms allow)                                          */
+int lifeapi_transform_offsets_batch(const uint64_t *in, uint64_t *out, size_t n, uint32_t transform,
+                                    const int32_t *offsets, int device);
+int lifeapi_symmetricize_offsets_batch(const uint64_t *in, uint64_t *out, size_t n, uint32_t symmetry,
+                                       const int32_t *offsets, int device);
+int lifeapi_convolve_pair_batch(const uint64_t *a, const uint64_t *b, uint32_t transform, uint64_t *out,
+                                size_t n, int device);
+int lifeapi_intersecting_offsets_batch(const uint64_t *pat1, const uint64_t *pat2, uint32_t symmetry,
+                                       uint64_t *out, size_t n, int device);
+int lifeapi_halve_batch(const uint64_t *in, uint64_t *out, size_t n, uint32_t mode, int device);
+int lifeapi_skew_batch(const uint64_t *in, uint64_t *out, size_t n, int inverse, int device);
 int lifeapi_bounds_batch(const uint64_t *states, int32_t *bounds, size_t n, int device);
 int lifeapi_symmetry_orbit_batch(const uint64_t *states, uint64_t *images, uint8_t *first, size_t n,
                                  int device);

@@ -669,6 +669,94 @@ int lifeapi_symmetricize_batch(const uint64_t *in, uint64_t *out, size_t n, uint
   });
 }
 
+// the same with an offset per universe, staged beside the states
+static int offsets_batch(const uint64_t *in, uint64_t *out, size_t n, const int32_t *offsets, int device,
+                         const char *what, const std::function<int(const uint64_t *, uint64_t *, size_t,
+                                                                   const int32_t *, hipStream_t)> &dev) {
+  if (n == 0) return LIFEAPI_OK;
+  const int rc = check_batch(in, out, n);
+  if (rc != LIFEAPI_OK) return rc;
+  if (!offsets || ((uintptr_t)offsets & 3u)) return fail(LIFEAPI_E_INVALID, "null or misaligned offsets to %s", what);
+  if (ranges_overlap(offsets, n * 8, out, n * 512))
+    return fail(LIFEAPI_E_INVALID, "offsets overlaps the output batch of %s", what);
+  return host_batch(n, device, {{in, out, 512}, {offsets, nullptr, 8}}, [=](void *const *d, size_t m, hipStream_t s) {
+    return dev((const uint64_t *)d[0], (uint64_t *)d[0], m, (const int32_t *)d[1], s);
+  });
+}
+
+int lifeapi_transform_offsets_batch(const uint64_t *in, uint64_t *out, size_t n, uint32_t transform,
+                                    const int32_t *offsets, int device) {
+  if (transform > 15) return fail(LIFEAPI_E_INVALID, "lifeapi_transform_offsets_batch: transform must be 0..15%s");
+  return offsets_batch(in, out, n, offsets, device, "lifeapi_transform_offsets_batch",
+                       [=](const uint64_t *di, uint64_t *dout, size_t m, const int32_t *dofs, hipStream_t s) {
+                         return lifeapi_transform_offsets_batch_dev(di, dout, m, transform, dofs, s);
+                       });
+}
+
+int lifeapi_symmetricize_offsets_batch(const uint64_t *in, uint64_t *out, size_t n, uint32_t symmetry,
+                                       const int32_t *offsets, int device) {
+  // (the symmetry is checked before n, as in the *_dev call: no device is touched)
+  const int rc = lifeapi_symmetricize_offsets_batch_dev(nullptr, nullptr, 0, symmetry, nullptr, nullptr);
+  if (rc != LIFEAPI_OK) return rc;
+  return offsets_batch(in, out, n, offsets, device, "lifeapi_symmetricize_offsets_batch",
+                       [=](const uint64_t *di, uint64_t *dout, size_t m, const int32_t *dofs, hipStream_t s) {
+                         return lifeapi_symmetricize_offsets_batch_dev(di, dout, m, symmetry, dofs, s);
+                       });
+}
+
+// a.Convolve(b.Transformed(t)) / IntersectingOffsets: the first operand's
+// staging slot doubles as the device output; b == a is staged once
+static int pair_batch(const uint64_t *a, const uint64_t *b, uint32_t code, bool intersecting, uint64_t *out, size_t n,
+                      int device) {
+  // (the code is checked before n, as in the *_dev calls: no device is touched)
+  int rc = intersecting ? lifeapi_intersecting_offsets_batch_dev(nullptr, nullptr, code, nullptr, 0, nullptr)
+                        : lifeapi_convolve_pair_batch_dev(nullptr, nullptr, code, nullptr, 0, nullptr);
+  if (rc != LIFEAPI_OK || n == 0) return rc;
+  rc = check_batch(a, out, n);
+  if (rc == LIFEAPI_OK) rc = check_batch(b, out, n);
+  if (rc == LIFEAPI_OK && a != b && ranges_overlap(a, n * 512, b, n * 512))
+    rc = fail(LIFEAPI_E_INVALID, "the operands overlap (only the same batch twice is allowed)%s");
+  if (rc != LIFEAPI_OK) return rc;
+  const auto dev = [=](const uint64_t *da, const uint64_t *db, size_t m, hipStream_t s) {
+    return intersecting ? lifeapi_intersecting_offsets_batch_dev(da, db, code, (uint64_t *)da, m, s)
+                        : lifeapi_convolve_pair_batch_dev(da, db, code, (uint64_t *)da, m, s);
+  };
+  if (a == b)
+    return host_batch(n, device, {{a, out, 512}}, [=](void *const *d, size_t m, hipStream_t s) {
+      return dev((const uint64_t *)d[0], (const uint64_t *)d[0], m, s);
+    });
+  return host_batch(n, device, {{a, out, 512}, {b, nullptr, 512}}, [=](void *const *d, size_t m, hipStream_t s) {
+    return dev((const uint64_t *)d[0], (const uint64_t *)d[1], m, s);
+  });
+}
+
+int lifeapi_convolve_pair_batch(const uint64_t *a, const uint64_t *b, uint32_t transform, uint64_t *out, size_t n,
+                                int device) {
+  return pair_batch(a, b, transform, false, out, n, device);
+}
+
+int lifeapi_intersecting_offsets_batch(const uint64_t *pat1, const uint64_t *pat2, uint32_t symmetry, uint64_t *out,
+                                       size_t n, int device) {
+  return pair_batch(pat1, pat2, symmetry, true, out, n, device);
+}
+
+int lifeapi_halve_batch(const uint64_t *in, uint64_t *out, size_t n, uint32_t mode, int device) {
+  if (mode > 2) return fail(LIFEAPI_E_INVALID, "lifeapi_halve_batch: mode must be 0 (Halve), 1 (HalveX) or 2 (HalveY)%s");
+  const int rc = check_batch(in, out, n);
+  if (rc != LIFEAPI_OK || n == 0) return rc;
+  return host_batch(n, device, {{in, out, 512}}, [=](void *const *d, size_t m, hipStream_t s) {
+    return lifeapi_halve_batch_dev((const uint64_t *)d[0], (uint64_t *)d[0], m, mode, s);
+  });
+}
+
+int lifeapi_skew_batch(const uint64_t *in, uint64_t *out, size_t n, int inverse, int device) {
+  const int rc = check_batch(in, out, n);
+  if (rc != LIFEAPI_OK || n == 0) return rc;
+  return host_batch(n, device, {{in, out, 512}}, [=](void *const *d, size_t m, hipStream_t s) {
+    return lifeapi_skew_batch_dev((const uint64_t *)d[0], (uint64_t *)d[0], m, inverse, s);
+  });
+}
+
 int lifeapi_bounds_batch(const uint64_t *states, int32_t *bounds, size_t n, int device) {
   if (n == 0) return LIFEAPI_OK;
   if (!states || !bounds || !aligned8(states)) return fail(LIFEAPI_E_INVALID, "bad pointer to lifeapi_bounds_batch%s");

@@ -64,6 +64,122 @@ struct Affine {
 
 namespace {
 
+// ---- the descriptors, shared by the host (one offset per launch) and the
+// kernels that take an offset per universe ----
+
+// A forward affine map of the torus, (x, y) -> (sx x + bx, sy y + by), or
+// with `swap` (sx y + bx, sy x + by): where the cell at (x, y) goes.
+struct Forward {
+  bool swap;
+  int sx, sy;
+  long long bx, by;
+};
+
+// The 16 SymmetryTransforms in the enum's order (Symmetry.hpp:7-26), read
+// off Transform (Symmetry.hpp:105-173): FlipX is (x, -y - 1), FlipY
+// (-x - 1, y), Transpose(false) (y, x), Transpose(true) (-y - 1, -x - 1),
+// Move(a, b) adds (a, b).
+constexpr Forward kTransforms[16] = {
+    {false, 1, 1, 0, 0},     // Identity
+    {false, 1, -1, 0, -1},   // ReflectAcrossXEven
+    {false, 1, -1, 0, 0},    // ReflectAcrossX
+    {false, -1, 1, -1, 0},   // ReflectAcrossYEven
+    {false, -1, 1, 0, 0},    // ReflectAcrossY
+    {true, -1, 1, -1, 0},    // Rotate90Even
+    {true, -1, 1, 0, 0},     // Rotate90
+    {true, 1, -1, 0, -1},    // Rotate270Even
+    {true, 1, -1, 0, 0},     // Rotate270
+    {false, -1, -1, 0, 0},   // Rotate180OddBoth
+    {false, -1, -1, -1, 0},  // Rotate180EvenHorizontal
+    {false, -1, -1, 0, -1},  // Rotate180EvenVertical
+    {false, -1, -1, -1, -1}, // Rotate180EvenBoth
+    {true, 1, 1, 0, 0},      // ReflectAcrossYeqX
+    {true, -1, -1, -1, -1},  // ReflectAcrossYeqNegX
+    {true, -1, -1, 0, 0},    // ReflectAcrossYeqNegXP1
+};
+
+__host__ __device__ inline Forward moved(Forward f, long long dx, long long dy) {
+  f.bx += dx;
+  f.by += dy;
+  return f;
+}
+
+__host__ __device__ inline uint32_t mod64(long long v) { return (uint32_t)(((v % 64) + 64) % 64); }
+
+// The map read backwards, as the kernels apply it:
+// out(X, Y) = in(sx (X - bx), sy (Y - by)); with swap out(X, Y) = g(Y, X),
+// g(u, v) = in(sy (u - by), sx (v - bx)).
+__host__ __device__ inline Affine backwards(const Forward &f) {
+  const int cs = f.swap ? f.sy : f.sx, rs = f.swap ? f.sx : f.sy;
+  const long long cb = f.swap ? f.by : f.bx, rb = f.swap ? f.bx : f.by;
+  Affine a;
+  a.colflip = cs < 0;
+  a.coloff = mod64(-cs * cb);
+  a.rowflip = rs < 0;
+  const uint32_t r = mod64(-rs * rb);  // w'(y) = w(+-y + r)
+  a.rowrot = a.rowflip ? (63u - r) & 63u : r;
+  a.transpose = f.swap;
+  return a;
+}
+
+// PerpComponent (Symmetry.hpp:540-563) for the two diagonal reflections, in
+// the reference's own int arithmetic (truncating / and %): not a function of
+// the offset mod 64 alone
+__host__ __device__ inline void perp_diag(int ox, int oy, bool negative, int &px, int &py) {
+  const int x = (ox + 32) % 64 - 32, y = (oy + 32) % 64 - 32;
+  if (negative) {
+    px = py = ((x + y + 128) / 2) % 64;
+  } else {
+    px = ((x - y + 128) / 2) % 64;
+    py = ((-x + y + 128) / 2) % 64;
+  }
+}
+
+// StaticSymmetry values (Symmetry.hpp:57-79) Symmetricize defines
+enum : uint32_t { kC1 = 0, kD2AcrossX = 1, kD2AcrossY = 3, kD2negdiagodd = 5, kD2diagodd = 6, kC2 = 7, kC4 = 11,
+                  kD4 = 13, kD4diag = 17 };
+
+// Symmetricize(state, symmetry, {dx, dy}) as rounds of acc |= map(acc)
+// (Symmetry.hpp:565-654); -1 for a symmetry the reference leaves undefined
+__host__ __device__ inline int symmetricize_maps(uint32_t symmetry, int dx, int dy, Forward (&m)[2]) {
+  const long long x = dx, y = dy;
+  switch (symmetry) {
+  case kC1: return 0;
+  case kC2:  // FlipX, FlipY, Move(dx + 1, dy + 1)
+    m[0] = moved(kTransforms[12], x + 1, y + 1);
+    return 1;
+  case kC4:  // Rotate90, Move(offset); then FlipX, FlipY, Move(dx - dy + 1, dy + dx + 1)
+    m[0] = moved(kTransforms[6], x, y);
+    m[1] = moved(kTransforms[12], x - y + 1, y + x + 1);
+    return 2;
+  case kD2AcrossX:  // FlipX, Move(dx, dy + 1)
+    m[0] = moved(kTransforms[1], x, y + 1);
+    return 1;
+  case kD2AcrossY:  // FlipY, Move(dx + 1, dy)
+    m[0] = moved(kTransforms[3], x + 1, y);
+    return 1;
+  case kD2diagodd:  // ReflectAcrossYeqX, Move(offset)
+    m[0] = moved(kTransforms[13], x, y);
+    return 1;
+  case kD2negdiagodd:  // Transpose(true), Move(dx + 1, dy + 1)
+    m[0] = moved(kTransforms[14], x + 1, y + 1);
+    return 1;
+  case kD4:  // PerpComponent(ReflectAcrossX) = (0, dy), PerpComponent(ReflectAcrossY) = (dx, 0)
+    m[0] = moved(kTransforms[1], 0, y + 1);
+    m[1] = moved(kTransforms[3], x + 1, 0);
+    return 2;
+  case kD4diag: {
+    int px, py, qx, qy;
+    perp_diag(dx, dy, false, px, py);
+    perp_diag(dx, dy, true, qx, qy);
+    m[0] = moved(kTransforms[13], px, py);
+    m[1] = moved(kTransforms[14], (long long)qx + 1, (long long)qy + 1);
+    return 2;
+  }
+  default: return -1;
+  }
+}
+
 __device__ __forceinline__ int affine_col(int lane, const Affine &a) {
   return ((a.colflip ? -lane : lane) + (int)a.coloff) & (kWave - 1);
 }
@@ -209,6 +325,89 @@ __global__ __launch_bounds__(kBlock) void k_symmetricize(const uint64_t *in, uin
 #pragma unroll
         for (int k = 0; k < U; ++k) acc[k] = W{acc[k].lo | t[k].lo, acc[k].hi | t[k].hi};
       }
+#pragma unroll
+    for (int k = 0; k < U; ++k)
+      if (u0 + k < n) st<true>(out + (u0 + k) * kWave + lane, acc[k]);
+  }
+}
+
+// ---- an offset per universe ----
+// offsets: n x {dx, dy} int32.  Lanes 0 .. 2U-1 load the wave's 2U words with
+// one vector load; each universe's two come back wave-uniform by v_readlane,
+// and the wave builds that universe's Affine on the scalar unit from the same
+// descriptor code the host runs for the single-offset kernels.
+template <int U>
+__device__ __forceinline__ int load_offsets(const int32_t *__restrict__ offsets, uint64_t u0, uint64_t n, int lane) {
+  return lane < 2 * U && u0 * 2 + (uint64_t)lane < n * 2 ? offsets[u0 * 2 + lane] : 0;
+}
+__device__ __forceinline__ int offset_word(int o, int i) { return __builtin_amdgcn_readlane(o, i); }
+
+// out[u] = in[u].Transformed(t).Moved(offsets[u]), `base` the Forward of t:
+// k_transform with the permuted load index and the row rotate per universe
+template <bool TRANSPOSE, int U>
+__global__ __launch_bounds__(kBlock) void k_transform_offsets(const uint64_t *in, uint64_t *out, Forward base,
+                                                              const int32_t *__restrict__ offsets, uint64_t n) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  TransposeLane c;
+  if constexpr (TRANSPOSE) c = transpose_lane(lane);
+  const uint64_t groups = (n + U - 1) / U, stride = (uint64_t)gridDim.x * kWavesPerBlock;
+  for (uint64_t g = (uint64_t)blockIdx.x * kWavesPerBlock + wib; g < groups; g += stride) {
+    const uint64_t u0 = g * U;
+    const int o = load_offsets<U>(offsets, u0, n, lane);
+    Affine a[U];
+    W s[U];
+#pragma unroll
+    for (int k = 0; k < U; ++k) {
+      a[k] = backwards(moved(base, offset_word(o, 2 * k), offset_word(o, 2 * k + 1)));
+      s[k] = u0 + k < n ? ld<true>(in + (u0 + k) * kWave + affine_col(lane, a[k])) : W{0u, 0u};
+    }
+#pragma unroll
+    for (int k = 0; k < U; ++k) {
+      W one[1] = {s[k]};
+      affine_rows<1>(one, a[k]);
+      s[k] = one[0];
+      if constexpr (TRANSPOSE) s[k] = transpose64(s[k], c);
+    }
+#pragma unroll
+    for (int k = 0; k < U; ++k)
+      if (u0 + k < n) st<true>(out + (u0 + k) * kWave + lane, s[k]);
+  }
+}
+
+// out[u] = Symmetricize(in[u], symmetry, offsets[u]): k_symmetricize with the
+// maps of each universe built by the wave.  symmetry is one the host has
+// found defined (symmetricize_maps >= 0).
+template <int U>
+__global__ __launch_bounds__(kBlock) void k_symmetricize_offsets(const uint64_t *in, uint64_t *out,
+                                                                 uint32_t symmetry,
+                                                                 const int32_t *__restrict__ offsets, uint64_t n) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  const TransposeLane c = transpose_lane(lane);
+  const uint64_t groups = (n + U - 1) / U, stride = (uint64_t)gridDim.x * kWavesPerBlock;
+  for (uint64_t g = (uint64_t)blockIdx.x * kWavesPerBlock + wib; g < groups; g += stride) {
+    const uint64_t u0 = g * U;
+    const int o = load_offsets<U>(offsets, u0, n, lane);
+    W acc[U];
+#pragma unroll
+    for (int k = 0; k < U; ++k) acc[k] = u0 + k < n ? ld<true>(in + (u0 + k) * kWave + lane) : W{0u, 0u};
+    // one universe after another, its maps built just before they are applied
+    // (building all U universes' maps first and applying each round stage by
+    // stage across them was measured slower: 100 SGPRs, 7 waves per SIMD,
+    // +8 to 10 % on C2, C4 and D4diag, profiles/r18/README.md)
+#pragma unroll
+    for (int k = 0; k < U; ++k) {
+      Forward m[2] = {kTransforms[0], kTransforms[0]};
+      const int rounds = symmetricize_maps(symmetry, offset_word(o, 2 * k), offset_word(o, 2 * k + 1), m);
+#pragma unroll
+      for (int r = 0; r < 2; ++r)
+        if (r < rounds) {
+          W one[1] = {acc[k]}, t[1];
+          affine_apply<1>(t, one, backwards(m[r]), lane, c);
+          acc[k] = W{acc[k].lo | t[0].lo, acc[k].hi | t[0].hi};
+        }
+    }
 #pragma unroll
     for (int k = 0; k < U; ++k)
       if (u0 + k < n) st<true>(out + (u0 + k) * kWave + lane, acc[k]);

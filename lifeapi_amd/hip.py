@@ -85,6 +85,18 @@ _SIGS = {
     "lifeapi_symmetricize_batch": ([_vp, _vp, _sz, _u32, _int, _int, _int], _int),
     "lifeapi_bounds_batch": ([_vp, _vp, _sz, _int], _int),
     "lifeapi_symmetry_orbit_batch": ([_vp, _vp, _vp, _sz, _int], _int),
+    "lifeapi_transform_offsets_batch_dev": ([_vp, _vp, _sz, _u32, _vp, _vp], _int),
+    "lifeapi_symmetricize_offsets_batch_dev": ([_vp, _vp, _sz, _u32, _vp, _vp], _int),
+    "lifeapi_convolve_pair_batch_dev": ([_vp, _vp, _u32, _vp, _sz, _vp], _int),
+    "lifeapi_intersecting_offsets_batch_dev": ([_vp, _vp, _u32, _vp, _sz, _vp], _int),
+    "lifeapi_halve_batch_dev": ([_vp, _vp, _sz, _u32, _vp], _int),
+    "lifeapi_skew_batch_dev": ([_vp, _vp, _sz, _int, _vp], _int),
+    "lifeapi_transform_offsets_batch": ([_vp, _vp, _sz, _u32, _vp, _int], _int),
+    "lifeapi_symmetricize_offsets_batch": ([_vp, _vp, _sz, _u32, _vp, _int], _int),
+    "lifeapi_convolve_pair_batch": ([_vp, _vp, _u32, _vp, _sz, _int], _int),
+    "lifeapi_intersecting_offsets_batch": ([_vp, _vp, _u32, _vp, _sz, _int], _int),
+    "lifeapi_halve_batch": ([_vp, _vp, _sz, _u32, _int], _int),
+    "lifeapi_skew_batch": ([_vp, _vp, _sz, _int, _int], _int),
     "lifeapi_first_on_batch_dev": ([_vp, _vp, _sz, _vp], _int),
     "lifeapi_component_containing_batch_dev": ([_vp, _vp, _int, _vp, _vp, _sz, _vp], _int),
     "lifeapi_components_batch_dev": ([_vp, _vp, _vp, _vp, _u32, _sz, _vp], _int),
@@ -313,6 +325,89 @@ def symmetry_orbit(states: torch.Tensor, images: bool = True, first: bool = True
     return (img, fst) if images and first else img if images else fst
 
 
+# the transform IntersectingOffsets applies to pat1, by symmetry (Symmetry.hpp:733-767)
+INTERSECTING_TRANSFORMS = {"C2": "Identity", "C4": "Rotate270", "D2AcrossX": "ReflectAcrossY",
+                           "D2AcrossY": "ReflectAcrossX", "D2diagodd": "ReflectAcrossYeqNegXP1",
+                           "D2negdiagodd": "ReflectAcrossYeqX"}
+HALVE_MODES = ("Halve", "HalveX", "HalveY")
+
+
+def _offsets(offsets: torch.Tensor, n: int) -> torch.Tensor:
+    """(n, 2) int32 {dx, dy} on the device."""
+    if not offsets.is_cuda or offsets.dtype != torch.int32 or not offsets.is_contiguous() or offsets.numel() != 2 * n:
+        raise ValueError("offsets must be a contiguous int32 device tensor of shape (n, 2)")
+    return offsets
+
+
+def transform_offsets(states: torch.Tensor, t: int | str, offsets: torch.Tensor, out: torch.Tensor | None = None,
+                      stream=None) -> torch.Tensor:
+    """:func:`transform` with universe u moved by ``offsets[u]`` ((n, 2) int32); ``out`` may be ``states``."""
+    n = _universes(states)
+    out = _out_like(states, out, n)
+    _check(lib.lifeapi_transform_offsets_batch_dev(states.data_ptr(), out.data_ptr(), n, _enum(t, TRANSFORMS),
+                                                   _offsets(offsets, n).data_ptr(), _stream(stream)))
+    return out
+
+
+def symmetricize_offsets(states: torch.Tensor, symmetry: int | str, offsets: torch.Tensor,
+                         out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+    """:func:`symmetricize` with universe u taking ``offsets[u]`` ((n, 2) int32); ``out`` may be ``states``."""
+    n = _universes(states)
+    out = _out_like(states, out, n)
+    _check(lib.lifeapi_symmetricize_offsets_batch_dev(states.data_ptr(), out.data_ptr(), n,
+                                                      _enum(symmetry, SYMMETRIES), _offsets(offsets, n).data_ptr(),
+                                                      _stream(stream)))
+    return out
+
+
+def convolve_pair(a: torch.Tensor, b: torch.Tensor | None = None, t: int | str = 0,
+                  out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+    """Per-universe ``a[u].Convolve(b[u].Transformed(t))`` (LifeAPI.hpp:1293-1370,
+    Symmetry.hpp:105-173); ``b=None`` is ``a`` itself; ``out`` may be ``a`` or ``b``."""
+    n = _universes(a, "a")
+    b = a if b is None else b
+    if _universes(b, "b") != n:
+        raise ValueError("b has a different number of universes")
+    out = _out_like(a, out, n)
+    _check(lib.lifeapi_convolve_pair_batch_dev(a.data_ptr(), b.data_ptr(), _enum(t, TRANSFORMS), out.data_ptr(), n,
+                                               _stream(stream)))
+    return out
+
+
+def intersecting_offsets(pat1: torch.Tensor, symmetry: int | str, pat2: torch.Tensor | None = None,
+                         out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+    """Per-universe ``IntersectingOffsets(pat1, pat2, symmetry)`` (Symmetry.hpp:729-768);
+    ``pat2=None`` is ``IntersectingOffsets(active, symmetry)`` (Symmetry.hpp:770-772);
+    ``symmetry`` a StaticSymmetry's value or name; ``out`` may be ``pat1`` or ``pat2``."""
+    n = _universes(pat1, "pat1")
+    pat2 = pat1 if pat2 is None else pat2
+    if _universes(pat2, "pat2") != n:
+        raise ValueError("pat2 has a different number of universes")
+    out = _out_like(pat1, out, n)
+    _check(lib.lifeapi_intersecting_offsets_batch_dev(pat1.data_ptr(), pat2.data_ptr(), _enum(symmetry, SYMMETRIES),
+                                                      out.data_ptr(), n, _stream(stream)))
+    return out
+
+
+def halve(states: torch.Tensor, mode: int | str = 0, out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+    """Per-universe ``Halve()`` (mode 0), ``HalveX()`` (1) or ``HalveY()`` (2)
+    (Symmetry.hpp:681-709), by value or name; ``out`` may be ``states``."""
+    n = _universes(states)
+    out = _out_like(states, out, n)
+    _check(lib.lifeapi_halve_batch_dev(states.data_ptr(), out.data_ptr(), n, _enum(mode, HALVE_MODES),
+                                       _stream(stream)))
+    return out
+
+
+def skew(states: torch.Tensor, inverse: bool = False, out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+    """Per-universe ``Skew()`` or, with ``inverse``, ``InvSkew()`` (Symmetry.hpp:711-727);
+    ``out`` may be ``states``."""
+    n = _universes(states)
+    out = _out_like(states, out, n)
+    _check(lib.lifeapi_skew_batch_dev(states.data_ptr(), out.data_ptr(), n, int(bool(inverse)), _stream(stream)))
+    return out
+
+
 def _corona(corona) -> np.ndarray | None:
     """The corona as the 64 host words the C ABI reads before it returns
     (None = the reference's default); a device tensor is brought to the host."""
@@ -508,6 +603,80 @@ def symmetry_orbit_host(states: np.ndarray, images: bool = True, first: bool = T
     _check(lib.lifeapi_symmetry_orbit_batch(src.ctypes.data, img.ctypes.data if images else None,
                                             fst.ctypes.data if first else None, n, device))
     return (img, fst) if images and first else img if images else fst
+
+
+def _host_offsets(offsets: np.ndarray, n: int) -> np.ndarray:
+    o = np.ascontiguousarray(offsets, dtype=np.int32)
+    if o.size != 2 * n:
+        raise ValueError("offsets must hold n x {dx, dy}")
+    return o
+
+
+def transform_offsets_host(states: np.ndarray, t: int | str, offsets: np.ndarray, out: np.ndarray | None = None,
+                           device: int = 0) -> np.ndarray:
+    """Host-pointer ``lifeapi_transform_offsets_batch``."""
+    src = _host_u64(states)
+    o = _host_offsets(offsets, src.size // N)
+    dst = np.empty_like(src) if out is None else out
+    _check(lib.lifeapi_transform_offsets_batch(src.ctypes.data, dst.ctypes.data, src.size // N,
+                                               _enum(t, TRANSFORMS), o.ctypes.data, device))
+    return dst
+
+
+def symmetricize_offsets_host(states: np.ndarray, symmetry: int | str, offsets: np.ndarray,
+                              out: np.ndarray | None = None, device: int = 0) -> np.ndarray:
+    """Host-pointer ``lifeapi_symmetricize_offsets_batch``."""
+    src = _host_u64(states)
+    o = _host_offsets(offsets, src.size // N)
+    dst = np.empty_like(src) if out is None else out
+    _check(lib.lifeapi_symmetricize_offsets_batch(src.ctypes.data, dst.ctypes.data, src.size // N,
+                                                  _enum(symmetry, SYMMETRIES), o.ctypes.data, device))
+    return dst
+
+
+def _host_pair(a: np.ndarray, b: np.ndarray | None) -> tuple:
+    x = _host_u64(a)
+    y = x if b is None or b is a else _host_u64(b)
+    if y.size != x.size:
+        raise ValueError("the operands hold different numbers of universes")
+    return x, y
+
+
+def convolve_pair_host(a: np.ndarray, b: np.ndarray | None = None, t: int | str = 0, out: np.ndarray | None = None,
+                       device: int = 0) -> np.ndarray:
+    """Host-pointer ``lifeapi_convolve_pair_batch``; ``b=None`` is ``a`` itself."""
+    x, y = _host_pair(a, b)
+    dst = np.empty_like(x) if out is None else out
+    _check(lib.lifeapi_convolve_pair_batch(x.ctypes.data, y.ctypes.data, _enum(t, TRANSFORMS), dst.ctypes.data,
+                                           x.size // N, device))
+    return dst
+
+
+def intersecting_offsets_host(pat1: np.ndarray, symmetry: int | str, pat2: np.ndarray | None = None,
+                              out: np.ndarray | None = None, device: int = 0) -> np.ndarray:
+    """Host-pointer ``lifeapi_intersecting_offsets_batch``; ``pat2=None`` is ``pat1`` itself."""
+    x, y = _host_pair(pat1, pat2)
+    dst = np.empty_like(x) if out is None else out
+    _check(lib.lifeapi_intersecting_offsets_batch(x.ctypes.data, y.ctypes.data, _enum(symmetry, SYMMETRIES),
+                                                  dst.ctypes.data, x.size // N, device))
+    return dst
+
+
+def halve_host(states: np.ndarray, mode: int | str = 0, out: np.ndarray | None = None, device: int = 0) -> np.ndarray:
+    """Host-pointer ``lifeapi_halve_batch``."""
+    src = _host_u64(states)
+    dst = np.empty_like(src) if out is None else out
+    _check(lib.lifeapi_halve_batch(src.ctypes.data, dst.ctypes.data, src.size // N, _enum(mode, HALVE_MODES), device))
+    return dst
+
+
+def skew_host(states: np.ndarray, inverse: bool = False, out: np.ndarray | None = None,
+              device: int = 0) -> np.ndarray:
+    """Host-pointer ``lifeapi_skew_batch``."""
+    src = _host_u64(states)
+    dst = np.empty_like(src) if out is None else out
+    _check(lib.lifeapi_skew_batch(src.ctypes.data, dst.ctypes.data, src.size // N, int(bool(inverse)), device))
+    return dst
 
 
 def first_on_host(states: np.ndarray, device: int = 0) -> np.ndarray:

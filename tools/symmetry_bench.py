@@ -3,8 +3,9 @@ of the same run, in one process on one GPU:
 
     python tools/symmetry_bench.py [--n 1048576] [--rounds 7] [--out FILE]
 
-Transform and Symmetricize move what the step moves (512 B in, 512 B out per
-universe); XYBounds reads 512 B and writes 16, the mask-only orbit reads 512 B
+Transform, Symmetricize, Halve and Skew move what the step moves (512 B in,
+512 B out per universe), the per-universe-offset forms 8 B more;
+IntersectingOffsets reads one batch in the self form and two otherwise; XYBounds reads 512 B and writes 16, the mask-only orbit reads 512 B
 and writes 1, the orbit with images writes 8 x 512 B.  Every case is timed two
 ways with device events, warmed up, over `rounds` alternating rounds (each
 round runs every case once, in turn): alone, each launch after the 768 MiB
@@ -49,6 +50,18 @@ def main():
     def scrub():
         torch.sum(scrub_buf, 0, out=sink)
 
+    # one 16-cell region (a 4 x 4 block) and one 3-cell region per universe, placed by the universe's index;
+    # the shared pattern of the yardstick is universe 0's block; offsets in [-200, 200]
+    u = torch.arange(n, device="cuda")
+    col, row = u % 55, (u * 7) % 58
+    blocks, threes = torch.zeros_like(x), torch.zeros_like(x)
+    for j in range(4):
+        blocks[u, col + j] = torch.bitwise_left_shift(torch.full_like(u, 15), row)
+    for j, (dc, dr) in enumerate(((0, 0), (5, 2), (9, 1))):
+        threes[u, col + dc] = torch.bitwise_left_shift(torch.ones_like(u), row + dr)
+    shared = blocks[:1].clone()
+    offsets = torch.randint(-200, 201, (n, 2), dtype=torch.int32, device="cuda")
+
     def orbit(img):
         hip._check(hip.lib.lifeapi_symmetry_orbit_batch_dev(x.data_ptr(), images.data_ptr() if img else None,
                                                             first.data_ptr(), n, stream))
@@ -63,6 +76,22 @@ def main():
         ("symmetricize_c2", lambda: hip.symmetricize(x, "C2", 7, -3, out=y), io),
         ("symmetricize_c4", lambda: hip.symmetricize(x, "C4", 7, -3, out=y), io),
         ("symmetricize_d4diag", lambda: hip.symmetricize(x, "D4diag", 7, -3, out=y), io),
+        ("transform_offsets_identity", lambda: hip.transform_offsets(x, "Identity", offsets, out=y), io + 8),
+        ("transform_offsets_rotate90", lambda: hip.transform_offsets(x, "Rotate90", offsets, out=y), io + 8),
+        ("symmetricize_offsets_c2", lambda: hip.symmetricize_offsets(x, "C2", offsets, out=y), io + 8),
+        ("symmetricize_offsets_c4", lambda: hip.symmetricize_offsets(x, "C4", offsets, out=y), io + 8),
+        ("symmetricize_offsets_d4diag", lambda: hip.symmetricize_offsets(x, "D4diag", offsets, out=y), io + 8),
+        ("halve", lambda: hip.halve(x, "Halve", out=y), io),
+        ("halve_y", lambda: hip.halve(x, "HalveY", out=y), io),
+        ("skew", lambda: hip.skew(x, out=y), io),
+        # IntersectingOffsets(active, sym) of one 16-cell region per universe, next to Convolve of the same
+        # batch with one shared 16-cell pattern; then a half-density batch against 3-cell regions, both orders
+        ("convolve_shared_16", lambda: hip.convolve(blocks, shared, out=y), io),
+        ("intersecting_self_c2", lambda: hip.intersecting_offsets(blocks, "C2", out=y), io),
+        ("intersecting_self_d2acrossx", lambda: hip.intersecting_offsets(blocks, "D2AcrossX", out=y), io),
+        ("intersecting_self_d2diagodd", lambda: hip.intersecting_offsets(blocks, "D2diagodd", out=y), io),
+        ("pair_dense_x_3cells", lambda: hip.convolve_pair(x, threes, out=y), io + 512),
+        ("pair_3cells_x_dense", lambda: hip.convolve_pair(threes, x, out=y), io + 512),
         ("bounds", lambda: hip._check(hip.lib.lifeapi_bounds_batch_dev(x.data_ptr(), bounds.data_ptr(), n, stream)),
          528),
         ("orbit_mask_only", lambda: orbit(False), 513),
