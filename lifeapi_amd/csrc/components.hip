@@ -45,28 +45,18 @@ int classify(const uint64_t *corona, Corona &c) {
   return kGeneral;
 }
 
-// a per-universe output of `bytes` each: aligned, clear of the states
-int check_side(const void *p, size_t align, size_t bytes, const void *d_states, size_t n, const char *what) {
-  if ((uintptr_t)p & (align - 1)) return fail(LIFEAPI_E_INVALID, "misaligned output of %s", what);
-  if (n > SIZE_MAX / bytes || ranges_overlap(p, n * bytes, d_states, n * 512))
-    return fail(LIFEAPI_E_INVALID, "an output of %s overlaps the input batch", what);
-  return LIFEAPI_OK;
-}
-
 template <int KIND>
 int launch_containing(void *stream, const uint64_t *d_states, const uint64_t *d_seeds, int per, const Corona &c,
                       uint64_t *d_out, size_t n) {
-  return launch(k_component_containing<KIND, kContainingU>, "k_component_containing launch",
-                Grid{(n + kContainingU - 1) / kContainingU}, stream, Written{d_out, (uint64_t)n * 512}, d_states,
-                d_seeds, per ? 1u : 0u, c, d_out, n);
+  return launch_groups(k_component_containing<KIND, kContainingU>, "k_component_containing launch", kContainingU,
+                       stream, d_out, kStateBytes, n, d_states, d_seeds, per ? 1u : 0u, c, d_out, n);
 }
 
 template <int KIND>
 int launch_components(void *stream, const uint64_t *d_states, const Corona &c, uint32_t *d_count,
                       uint64_t *d_components, uint32_t max_components, size_t n) {
-  return launch(k_components<KIND>, "k_components launch", Grid{n}, stream,
-                d_components ? Written{d_components, (uint64_t)n * max_components * 512} : kWritesNoBatch, d_states, c,
-                d_count, d_components, max_components, n);
+  return launch_groups(k_components<KIND>, "k_components launch", 1, stream, d_components,
+                       (uint64_t)max_components * kStateBytes, n, d_states, c, d_count, d_components, max_components, n);
 }
 
 }  // namespace
@@ -79,8 +69,8 @@ int lifeapi_first_on_batch_dev(const uint64_t *d_states, int32_t *d_cells, size_
   int rc = check_batch(d_states, d_states, n);
   if (rc == LIFEAPI_OK) rc = check_side(d_cells, 4, 8, d_states, n, "lifeapi_first_on_batch_dev");
   if (rc != LIFEAPI_OK) return rc;
-  return launch(k_first_on<kFirstOnU>, "k_first_on launch", Grid{(n + kFirstOnU - 1) / kFirstOnU}, stream,
-                kWritesNoBatch, d_states, d_cells, n);
+  return launch_groups(k_first_on<kFirstOnU>, "k_first_on launch", kFirstOnU, stream, nullptr, 0, n, d_states, d_cells,
+                       n);
 }
 
 int lifeapi_component_containing_batch_dev(const uint64_t *d_states, const uint64_t *d_seeds, int per_universe_seeds,

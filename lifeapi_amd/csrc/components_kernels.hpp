@@ -143,12 +143,12 @@ __device__ __forceinline__ bool first_on(W s, uint32_t &x, uint32_t &y) {
 template <int U>
 __global__ __launch_bounds__(kBlock) void k_first_on(const uint64_t *__restrict__ in, int32_t *__restrict__ cells,
                                                      uint64_t n) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
-  const uint64_t groups = (n + U - 1) / U, stride = (uint64_t)gridDim.x * kWavesPerBlock;
-  for (uint64_t g = (uint64_t)blockIdx.x * kWavesPerBlock + wib; g < groups; g += stride) {
+  const int lane = wave_lane(), wib = wave_in_block();
+  const WaveGroups at = wave_groups<U>(wib, n);
+  for (uint64_t g = at.first; g < at.groups; g += at.stride) {
     const uint64_t u0 = g * U;
     W s[U];
+    // (spelled out: through load_object this kernel's listing changes)
 #pragma unroll
     for (int k = 0; k < U; ++k) s[k] = u0 + k < n ? ld<true>(in + (u0 + k) * kWave + lane) : W{0u, 0u};
     int h = 0;
@@ -158,7 +158,7 @@ __global__ __launch_bounds__(kBlock) void k_first_on(const uint64_t *__restrict_
       const bool on = first_on(s[k], x, y);
       h = lane == 2 * k ? (on ? (int)x : -1) : lane == 2 * k + 1 ? (on ? (int)y : -1) : h;
     }
-    if (lane < 2 * U && u0 + (uint64_t)(lane >> 1) < n) cells[u0 * 2 + lane] = h;
+    if (holds_scalar<U, 2>(u0, n, lane)) cells[u0 * 2 + lane] = h;
   }
 }
 
@@ -170,25 +170,23 @@ template <int KIND, int U>
 __global__ __launch_bounds__(kBlock) void k_component_containing(const uint64_t *states, const uint64_t *seeds,
                                                                  uint32_t per_universe, Corona corona, uint64_t *out,
                                                                  uint64_t n) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  const int lane = wave_lane(), wib = wave_in_block();
   W pat{0u, 0u}, one{0u, 0u};
   if constexpr (KIND == kGeneral) pat = split(corona.w[lane]);
   if (!per_universe) one = split(seeds[lane]);
-  const uint64_t groups = (n + U - 1) / U, stride = (uint64_t)gridDim.x * kWavesPerBlock;
-  for (uint64_t g = (uint64_t)blockIdx.x * kWavesPerBlock + wib; g < groups; g += stride) {
+  const WaveGroups at = wave_groups<U>(wib, n);
+  for (uint64_t g = at.first; g < at.groups; g += at.stride) {
     const uint64_t u0 = g * U;
     W s[U], seed[U], res[U];
 #pragma unroll
     for (int k = 0; k < U; ++k) {
-      const bool live = u0 + k < n;
+      const bool live = u0 + k < n;  // (one guard for both loads: through load_object the listing changes)
       s[k] = live ? ld<true>(states + (u0 + k) * kWave + lane) : W{0u, 0u};
       seed[k] = !live ? W{0u, 0u} : per_universe ? ld<true>(seeds + (u0 + k) * kWave + lane) : one;
     }
     flood<KIND, U>(res, s, seed, pat, lane);
 #pragma unroll
-    for (int k = 0; k < U; ++k)
-      if (u0 + k < n) st<true>(out + (u0 + k) * kWave + lane, res[k]);
+    for (int k = 0; k < U; ++k) store_object(out, u0 + k, n, lane, res[k]);
   }
 }
 
@@ -200,12 +198,11 @@ template <int KIND>
 __global__ __launch_bounds__(kBlock) void k_components(const uint64_t *__restrict__ states, Corona corona,
                                                        uint32_t *__restrict__ count, uint64_t *__restrict__ components,
                                                        uint32_t max_components, uint64_t n) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  const int lane = wave_lane(), wib = wave_in_block();
   W pat{0u, 0u};
   if constexpr (KIND == kGeneral) pat = split(corona.w[lane]);
-  const uint64_t stride = (uint64_t)gridDim.x * kWavesPerBlock;
-  for (uint64_t u = (uint64_t)blockIdx.x * kWavesPerBlock + wib; u < n; u += stride) {
+  const WaveGroups at = wave_groups<1>(wib, n);
+  for (uint64_t u = at.first; u < at.groups; u += at.stride) {
     W rem[1] = {ld<true>(states + u * kWave + lane)};
     uint32_t found = 0;
     for (; found < kMaxComponents; ++found) {

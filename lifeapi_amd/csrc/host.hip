@@ -201,6 +201,28 @@ int check_batch(const void *in, const void *out, size_t n) {
   return LIFEAPI_OK;
 }
 
+int check_ptr(const char *fn, const Arg &a) {
+  if (!a.p) return fail(LIFEAPI_E_INVALID, (std::string(fn) + ": null " + a.name + "%s").c_str());
+  if (a.align8 && !aligned8(a.p))
+    return fail(LIFEAPI_E_INVALID, (std::string(fn) + ": misaligned " + a.name + "%s").c_str());
+  return LIFEAPI_OK;
+}
+int check_clear(const char *fn, const Arg &a, std::initializer_list<Arg> others) {
+  for (const Arg &o : others)
+    if (o.p && ranges_overlap(a.p, a.bytes, o.p, o.bytes))
+      return fail(LIFEAPI_E_INVALID, (std::string(fn) + ": " + a.name + " overlaps " + o.name + "%s").c_str());
+  return LIFEAPI_OK;
+}
+int check_n(const char *fn, size_t n) {
+  return n > SIZE_MAX / kStableBytes ? fail(LIFEAPI_E_INVALID, "%s: n too large", fn) : LIFEAPI_OK;
+}
+int check_side(const void *p, size_t align, size_t bytes, const void *d_states, size_t n, const char *what) {
+  if ((uintptr_t)p & (align - 1)) return fail(LIFEAPI_E_INVALID, "misaligned output of %s", what);
+  if (n > SIZE_MAX / bytes || ranges_overlap(p, n * bytes, d_states, n * kStateBytes))
+    return fail(LIFEAPI_E_INVALID, "an output of %s overlaps the input batch", what);
+  return LIFEAPI_OK;
+}
+
 unsigned grid_for(uint64_t waves_needed, int cus, int blocks_per_cu) {
   uint64_t blocks = (waves_needed + kWavesPerBlock - 1) / kWavesPerBlock;
   if (blocks_per_cu > 0) blocks = std::min<uint64_t>(blocks, (uint64_t)cus * blocks_per_cu);

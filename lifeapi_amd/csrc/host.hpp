@@ -34,6 +34,23 @@ inline bool ranges_overlap(const void *a, size_t abytes, const void *b, size_t b
 }
 // n universes in / out: non-null, 8-byte aligned, equal or disjoint
 int check_batch(const void *in, const void *out, size_t n);
+// The argument checks of the entry points that name the offending argument
+// (weld.hip, stable_test.hip): fn is the entry point, for the message.
+struct Arg {
+  const char *name;
+  const void *p;
+  size_t bytes;  // in all
+  bool align8 = true;
+};
+// non-null and, with align8, 8-byte aligned
+int check_ptr(const char *fn, const Arg &a);
+// a clear of every non-null array of `others` ("<a> overlaps <other>")
+int check_clear(const char *fn, const Arg &a, std::initializer_list<Arg> others);
+// n objects of any kind (the largest, a LifeStable) fit a size_t
+int check_n(const char *fn, size_t n);
+// a per-universe output of `bytes` each: aligned, clear of the states
+// (symmetry.hip, components.hip)
+int check_side(const void *p, size_t align, size_t bytes, const void *d_states, size_t n, const char *what);
 // blocks for `waves_needed` waves, capped at cus * blocks_per_cu (0 = no cap)
 unsigned grid_for(uint64_t waves_needed, int cus, int blocks_per_cu);
 // the launch's error state as a return code

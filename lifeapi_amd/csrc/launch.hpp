@@ -1,6 +1,7 @@
 // launch.hpp -- host only: the one way a *_dev entry point launches a kernel
-// (launch), with the batch it writes stated for the order book (Written), and
-// the order-keyed store policy (launch_order).  The book is in host.hip.
+// (launch), with the batch it writes stated for the order book (Written), the
+// order-keyed store policy (launch_order), and launch as the kernels with one
+// wave per group of objects take it (launch_groups).  The book is in host.hip.
 #pragma once
 
 #include <type_traits>
@@ -75,6 +76,18 @@ int launch(void (*kernel)(P...), const char *what, Grid g, void *stream, const W
     return fail(LIFEAPI_E_INVALID, "batch too large for one grid%s");
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, (hipStream_t)stream, args...);
   return launched(what);
+}
+
+// The launch of the kernels with one wave per group of U objects
+// (wave_groups.hpp): a wave for every group, so the kernels' loops only run
+// again on a grid capped at 2^30 blocks.  d_out is the batch written, of
+// bytes_per_object each, or null where the launch writes none (counts, cells,
+// bounds).
+template <class... P, class... A>
+int launch_groups(void (*kernel)(P...), const char *what, int U, void *stream, const void *d_out,
+                  uint64_t bytes_per_object, size_t n, A... args) {
+  return launch(kernel, what, Grid{(n + U - 1) / U}, stream,
+                d_out ? Written{d_out, (uint64_t)n * bytes_per_object} : kWritesNoBatch, args...);
 }
 
 }  // namespace lifeapi_impl

@@ -15,17 +15,9 @@ constexpr int kMatchU = 4, kInteractionU = 2;
 // the 64 device words of a pattern: non-null, aligned, not written by the call
 int check_pattern(const void *pat, const void *d_out, size_t n, const char *what) {
   if (!pat || !aligned8(pat)) return fail(LIFEAPI_E_INVALID, "null or misaligned pattern pointer to %s", what);
-  if (d_out && ranges_overlap(pat, 512, d_out, n * 512))
+  if (d_out && ranges_overlap(pat, kStateBytes, d_out, n * kStateBytes))
     return fail(LIFEAPI_E_INVALID, "the pattern overlaps the output batch of %s", what);
   return LIFEAPI_OK;
-}
-
-// one wave per group of U universes, a wave for every group (the kernels'
-// loops only run again on a grid capped at 2^30 blocks)
-template <class... P, class... A>
-int launch_groups(void (*kernel)(P...), const char *what, int U, void *stream, uint64_t *d_out, size_t n, A... args) {
-  return launch(kernel, what, Grid{(n + U - 1) / U}, stream,
-                d_out ? Written{d_out, (uint64_t)n * 512} : kWritesNoBatch, args...);
 }
 
 }  // namespace
@@ -46,7 +38,7 @@ int lifeapi_match_batch_dev(const uint64_t *d_states, const uint64_t *d_wanted, 
         ranges_overlap(d_count, n * 4, d_wanted, 512) || ranges_overlap(d_count, n * 4, d_unwanted, 512))
       return fail(LIFEAPI_E_INVALID, "lifeapi_match_batch_dev: d_count overlaps another argument%s");
   }
-  return launch_groups(k_match<kMatchU>, "k_match launch", kMatchU, stream, d_out, n, d_states, d_out, d_wanted,
+  return launch_groups(k_match<kMatchU>, "k_match launch", kMatchU, stream, d_out, kStateBytes, n, d_states, d_out, d_wanted,
                        d_unwanted, d_count, n);
 }
 
@@ -56,7 +48,7 @@ int lifeapi_convolve_batch_dev(const uint64_t *d_states, const uint64_t *d_patte
   int rc = check_batch(d_states, d_out, n);
   if (rc == LIFEAPI_OK) rc = check_pattern(d_pattern, d_out, n, "lifeapi_convolve_batch_dev");
   if (rc != LIFEAPI_OK) return rc;
-  return launch_groups(k_convolve<kMatchU>, "k_convolve launch", kMatchU, stream, d_out, n, d_states, d_out,
+  return launch_groups(k_convolve<kMatchU>, "k_convolve launch", kMatchU, stream, d_out, kStateBytes, n, d_states, d_out,
                        d_pattern, n);
 }
 
@@ -67,7 +59,7 @@ int lifeapi_interaction_offsets_batch_dev(const uint64_t *d_states, const uint64
   if (rc == LIFEAPI_OK) rc = check_pattern(d_other, d_out, n, "lifeapi_interaction_offsets_batch_dev");
   if (rc != LIFEAPI_OK) return rc;
   return launch_groups(k_interaction_offsets<kInteractionU>, "k_interaction_offsets launch", kInteractionU, stream,
-                       d_out, n, d_states, d_out, d_other, n);
+                       d_out, kStateBytes, n, d_states, d_out, d_other, n);
 }
 
 }  // extern "C"

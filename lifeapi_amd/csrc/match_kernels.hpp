@@ -8,7 +8,8 @@
 //   Match(w, u)(x, y)    = AND over (a, b) in w of  s(x + a, y + b)
 //                        & AND over (a, b) in u of ~s(x + a, y + b)
 // One wave per universe, lane = column, U universes per wave with their loads
-// issued first.  The pattern is one for the launch: each wave loads its 64
+// issued first (the loop and the guarded loads and stores: wave_groups.hpp).
+// The pattern is one for the launch: each wave loads its 64
 // words once (lane j = column j) and walks its cells in scalar loops -- the
 // populated columns from a ballot, a column's word from v_readlane, the set
 // rows from s_ff1.  For pattern column a the universe's column x -+ a comes
@@ -40,7 +41,7 @@
 // an eater 5.2-5.4 x (issue-bound).
 #pragma once
 
-#include "device.hpp"
+#include "wave_groups.hpp"
 
 namespace lifeapi_impl {
 namespace {
@@ -127,17 +128,17 @@ __global__ __launch_bounds__(kBlock) void k_match(const uint64_t *in, uint64_t *
                                                   const uint64_t *__restrict__ wanted,
                                                   const uint64_t *__restrict__ unwanted,
                                                   uint32_t *__restrict__ count, uint64_t n) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  const int lane = wave_lane(), wib = wave_in_block();
   const W w = split(wanted[lane]), uw = split(unwanted[lane]);
   const uint64_t care = __ballot((w.lo | w.hi | uw.lo | uw.hi) != 0u);
-  const uint64_t groups = (n + U - 1) / U, stride = (uint64_t)gridDim.x * kWavesPerBlock;
-  for (uint64_t g = (uint64_t)blockIdx.x * kWavesPerBlock + wib; g < groups; g += stride) {
+  const WaveGroups at = wave_groups<U>(wib, n);
+  for (uint64_t g = at.first; g < at.groups; g += at.stride) {
     const uint64_t u0 = g * U;
     W s[U], all[U], any[U];
 #pragma unroll
+    for (int k = 0; k < U; ++k) s[k] = load_object(in, u0 + k, n, lane);
+#pragma unroll
     for (int k = 0; k < U; ++k) {
-      s[k] = u0 + k < n ? ld<true>(in + (u0 + k) * kWave + lane) : W{0u, 0u};
       all[k] = W{~0u, ~0u};
       any[k] = W{0u, 0u};
     }
@@ -155,19 +156,16 @@ __global__ __launch_bounds__(kBlock) void k_match(const uint64_t *in, uint64_t *
     for (int k = 0; k < U; ++k) m[k] = W{all[k].lo & ~any[k].lo, all[k].hi & ~any[k].hi};
     if (out) {
 #pragma unroll
-      for (int k = 0; k < U; ++k)
-        if (u0 + k < n) st<true>(out + (u0 + k) * kWave + lane, m[k]);
+      for (int k = 0; k < U; ++k) store_object(out, u0 + k, n, lane, m[k]);
     }
     if (count) {
-      // lanes 0..U-1 store the U wave-uniform counts with one vector store
-      // (written out here: through a helper taking the counts by reference
-      // the compiler keeps them in LDS, as k_step_contains_split notes)
-      uint32_t h = 0;
+      uint32_t h = 0;  // lanes 0 .. U-1 store the U wave-uniform counts with one vector store
 #pragma unroll
       for (int k = 0; k < U; ++k) {
         const uint32_t c = wave_sum_u32_dpp((uint32_t)(__popc(m[k].lo) + __popc(m[k].hi)));
         h = lane == k ? c : h;
       }
+      // (spelled out: through holds_scalar this kernel's listing changes)
       if (lane < U && u0 + (uint64_t)lane < n) count[u0 + lane] = h;
     }
   }
@@ -177,23 +175,43 @@ __global__ __launch_bounds__(kBlock) void k_match(const uint64_t *in, uint64_t *
 template <int U>
 __global__ __launch_bounds__(kBlock) void k_convolve(const uint64_t *in, uint64_t *out,
                                                      const uint64_t *__restrict__ pattern, uint64_t n) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  const int lane = wave_lane(), wib = wave_in_block();
   const W pat = split(pattern[lane]);
-  const uint64_t groups = (n + U - 1) / U, stride = (uint64_t)gridDim.x * kWavesPerBlock;
-  for (uint64_t g = (uint64_t)blockIdx.x * kWavesPerBlock + wib; g < groups; g += stride) {
+  const WaveGroups at = wave_groups<U>(wib, n);
+  for (uint64_t g = at.first; g < at.groups; g += at.stride) {
     const uint64_t u0 = g * U;
     W s[U], acc[U];
 #pragma unroll
     for (int k = 0; k < U; ++k) {
-      s[k] = u0 + k < n ? ld<true>(in + (u0 + k) * kWave + lane) : W{0u, 0u};
+      s[k] = load_object(in, u0 + k, n, lane);
       acc[k] = W{0u, 0u};
     }
     dilate<U>(acc, s, pat, lane);
 #pragma unroll
-    for (int k = 0; k < U; ++k)
-      if (u0 + k < n) st<true>(out + (u0 + k) * kWave + lane, acc[k]);
+    for (int k = 0; k < U; ++k) store_object(out, u0 + k, n, lane, acc[k]);
   }
+}
+
+// The inclusive 3 x 3 count as four planes (CountNeighbourhood, LifeAPI.hpp:
+// 909-952, NeighbourCount.hpp:40-70): column-first, the two planes of each
+// column's vertical triple, then the FullAdds across the neighbour columns and
+// the carry.  (k_counts, stencil_kernels.hpp, has the same network inside the
+// kernel: a tuned family, left as it is.)
+struct Count4 {
+  uint64_t b3, b2, b1, b0;
+  __device__ __forceinline__ uint64_t exactly(unsigned n) const {
+    return (n & 1 ? b0 : ~b0) & (n & 2 ? b1 : ~b1) & (n & 4 ? b2 : ~b2) & (n & 8 ? b3 : ~b3);
+  }
+};
+__device__ __forceinline__ Count4 count4(uint64_t s, int lane) {
+  const W a = split(s), up = rot_up(a), dn = rot_dn(a);
+  const W c0 = lut3<kXor3>(up, dn, a), c1 = lut3<kMaj>(up, dn, a);
+  W L0, R0, L1, R1;
+  neighbours<XDPP>(c0, c1, L0, R0, L1, R1, nullptr, lane);
+  const uint64_t fs = join(lut3<kXor3>(L0, c0, R0)), fc = join(lut3<kMaj>(L0, c0, R0));
+  const uint64_t cs = join(lut3<kXor3>(L1, c1, R1)), cc = join(lut3<kMaj>(L1, c1, R1));
+  const uint64_t carry = fc & cs;
+  return Count4{cc & carry, cc ^ carry, fc ^ cs, fs};
 }
 
 // The seven planes InteractionOffsets convolves, of one side (LifeAPI.hpp:
@@ -202,20 +220,12 @@ __global__ __launch_bounds__(kBlock) void k_convolve(const uint64_t *in, uint64_
 //   1 count == 1 & ~state           4 count >= 4 & state
 //   2 count == 2 & ~state           5 count >= 2 & ~state
 //                                   6 count >= 1 & ~state
-// count = the inclusive 3x3 count, CountNeighbourhood's four planes
-// (LifeAPI.hpp:909-952) by k_counts' network (stencil_kernels.hpp, which
-// has it inside the kernel, not as a function: written again here from
-// device.hpp's primitives).
+// count = the inclusive 3x3 count (count4).
 constexpr int kPartner[7] = {0, 2, 1, 5, 6, 3, 4};
 __device__ __forceinline__ void interaction_planes(W a, W (&p)[7], int lane) {
-  const W up = rot_up(a), dn = rot_dn(a);
-  const W c0 = lut3<kXor3>(up, dn, a), c1 = lut3<kMaj>(up, dn, a);
-  W L0, R0, L1, R1;
-  neighbours<XDPP>(c0, c1, L0, R0, L1, R1, nullptr, lane);
-  const uint64_t fs = join(lut3<kXor3>(L0, c0, R0)), fc = join(lut3<kMaj>(L0, c0, R0));
-  const uint64_t cs = join(lut3<kXor3>(L1, c1, R1)), cc = join(lut3<kMaj>(L1, c1, R1));
-  const uint64_t s = join(a), carry = fc & cs;
-  const uint64_t b0 = fs, b1 = fc ^ cs, b2 = cc ^ carry, b3 = cc & carry, hi = b3 | b2;
+  const uint64_t s = join(a);
+  const Count4 c = count4(s, lane);
+  const uint64_t b0 = c.b0, b1 = c.b1, hi = c.b3 | c.b2;
   p[0] = a;
   p[1] = split(~hi & ~b1 & b0 & ~s);
   p[2] = split(~hi & b1 & ~b0 & ~s);
@@ -232,19 +242,18 @@ __device__ __forceinline__ void interaction_planes(W a, W (&p)[7], int lane) {
 template <int U>
 __global__ __launch_bounds__(kBlock) void k_interaction_offsets(const uint64_t *in, uint64_t *out,
                                                                 const uint64_t *__restrict__ other, uint64_t n) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  const int lane = wave_lane(), wib = wave_in_block();
   W bp[7];
   {
     const uint64_t o = __builtin_bitreverse64(other[(kWave - lane) & (kWave - 1)]);
     interaction_planes(split(o << 1 | o >> 63), bp, lane);
   }
-  const uint64_t groups = (n + U - 1) / U, stride = (uint64_t)gridDim.x * kWavesPerBlock;
-  for (uint64_t g = (uint64_t)blockIdx.x * kWavesPerBlock + wib; g < groups; g += stride) {
+  const WaveGroups at = wave_groups<U>(wib, n);
+  for (uint64_t g = at.first; g < at.groups; g += at.stride) {
     const uint64_t u0 = g * U;
     W s[U], acc[U], ap[U][7];
 #pragma unroll
-    for (int k = 0; k < U; ++k) s[k] = u0 + k < n ? ld<true>(in + (u0 + k) * kWave + lane) : W{0u, 0u};
+    for (int k = 0; k < U; ++k) s[k] = load_object(in, u0 + k, n, lane);
 #pragma unroll
     for (int k = 0; k < U; ++k) {
       interaction_planes(s[k], ap[k], lane);
@@ -258,8 +267,7 @@ __global__ __launch_bounds__(kBlock) void k_interaction_offsets(const uint64_t *
       dilate<U>(acc, src, bp[kPartner[i]], lane);
     }
 #pragma unroll
-    for (int k = 0; k < U; ++k)
-      if (u0 + k < n) st<true>(out + (u0 + k) * kWave + lane, acc[k]);
+    for (int k = 0; k < U; ++k) store_object(out, u0 + k, n, lane, acc[k]);
   }
 }
 

@@ -26,11 +26,6 @@ int intersecting_transform(uint32_t symmetry) {
   }
 }
 
-template <class... P, class... A>
-int launch_groups(void (*kernel)(P...), const char *what, int U, void *stream, uint64_t *d_out, size_t n, A... args) {
-  return launch(kernel, what, Grid{(n + U - 1) / U}, stream, Written{d_out, (uint64_t)n * 512}, args...);
-}
-
 }  // namespace
 
 extern "C" {
@@ -47,9 +42,9 @@ int lifeapi_convolve_pair_batch_dev(const uint64_t *d_a, const uint64_t *d_b, ui
   if (rc != LIFEAPI_OK) return rc;
   const Affine t = backwards(kTransforms[transform]);
   const uint32_t plain = transform == 0;
-  return d_a == d_b ? launch_groups(k_convolve_pair<true, kPairU>, "k_convolve_pair launch", kPairU, stream, d_out, n,
+  return d_a == d_b ? launch_groups(k_convolve_pair<true, kPairU>, "k_convolve_pair launch", kPairU, stream, d_out, kStateBytes, n,
                                     d_a, d_b, d_out, t, plain, n)
-                    : launch_groups(k_convolve_pair<false, kPairU>, "k_convolve_pair launch", kPairU, stream, d_out, n,
+                    : launch_groups(k_convolve_pair<false, kPairU>, "k_convolve_pair launch", kPairU, stream, d_out, kStateBytes, n,
                                     d_a, d_b, d_out, t, plain, n);
 }
 
@@ -68,14 +63,14 @@ int lifeapi_halve_batch_dev(const uint64_t *d_in, uint64_t *d_out, size_t n, uin
   if (n == 0) return LIFEAPI_OK;
   const int rc = check_batch(d_in, d_out, n);
   if (rc != LIFEAPI_OK) return rc;
-  return launch_groups(k_halve<kHalveU>, "k_halve launch", kHalveU, stream, d_out, n, d_in, d_out, mode, n);
+  return launch_groups(k_halve<kHalveU>, "k_halve launch", kHalveU, stream, d_out, kStateBytes, n, d_in, d_out, mode, n);
 }
 
 int lifeapi_skew_batch_dev(const uint64_t *d_in, uint64_t *d_out, size_t n, int inverse, void *stream) {
   if (n == 0) return LIFEAPI_OK;
   const int rc = check_batch(d_in, d_out, n);
   if (rc != LIFEAPI_OK) return rc;
-  return launch_groups(k_skew<kSkewU>, "k_skew launch", kSkewU, stream, d_out, n, d_in, d_out,
+  return launch_groups(k_skew<kSkewU>, "k_skew launch", kSkewU, stream, d_out, kStateBytes, n, d_in, d_out,
                        (uint32_t)(inverse != 0), n);
 }
 

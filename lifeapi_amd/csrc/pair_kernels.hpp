@@ -44,19 +44,18 @@ namespace {
 template <bool SELF, int U>
 __global__ __launch_bounds__(kBlock) void k_convolve_pair(const uint64_t *a, const uint64_t *b, uint64_t *out,
                                                           Affine t, uint32_t plain, uint64_t n) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  const int lane = wave_lane(), wib = wave_in_block();
   const TransposeLane c = transpose_lane(lane);
-  const uint64_t groups = (n + U - 1) / U, stride = (uint64_t)gridDim.x * kWavesPerBlock;
-  for (uint64_t g = (uint64_t)blockIdx.x * kWavesPerBlock + wib; g < groups; g += stride) {
+  const WaveGroups at = wave_groups<U>(wib, n);
+  for (uint64_t g = at.first; g < at.groups; g += at.stride) {
     const uint64_t u0 = g * U;
     W sa[U], sb[U], tb[U];
 #pragma unroll
-    for (int k = 0; k < U; ++k) sa[k] = u0 + k < n ? ld<true>(a + (u0 + k) * kWave + lane) : W{0u, 0u};
+    for (int k = 0; k < U; ++k) sa[k] = load_object(a, u0 + k, n, lane);
 #pragma unroll
     for (int k = 0; k < U; ++k) {
       if constexpr (SELF) sb[k] = sa[k];
-      else sb[k] = u0 + k < n ? ld<true>(b + (u0 + k) * kWave + lane) : W{0u, 0u};
+      else sb[k] = load_object(b, u0 + k, n, lane);
     }
     if (plain) {
 #pragma unroll
@@ -75,8 +74,7 @@ __global__ __launch_bounds__(kBlock) void k_convolve_pair(const uint64_t *a, con
       sa[k] = acc[0];
     }
 #pragma unroll
-    for (int k = 0; k < U; ++k)
-      if (u0 + k < n) st<true>(out + (u0 + k) * kWave + lane, sa[k]);
+    for (int k = 0; k < U; ++k) store_object(out, u0 + k, n, lane, sa[k]);
   }
 }
 
@@ -93,15 +91,14 @@ __device__ __forceinline__ uint32_t even_bits(uint32_t v) {
 // allowed: a wave loads its universes whole before it stores them
 template <int U>
 __global__ __launch_bounds__(kBlock) void k_halve(const uint64_t *in, uint64_t *out, uint32_t mode, uint64_t n) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  const int lane = wave_lane(), wib = wave_in_block();
   const int col = mode == 2 ? lane : 2 * (lane & 31);
-  const uint64_t groups = (n + U - 1) / U, stride = (uint64_t)gridDim.x * kWavesPerBlock;
-  for (uint64_t g = (uint64_t)blockIdx.x * kWavesPerBlock + wib; g < groups; g += stride) {
+  const WaveGroups at = wave_groups<U>(wib, n);
+  for (uint64_t g = at.first; g < at.groups; g += at.stride) {
     const uint64_t u0 = g * U;
     W s[U];
 #pragma unroll
-    for (int k = 0; k < U; ++k) s[k] = u0 + k < n ? ld<true>(in + (u0 + k) * kWave + col) : W{0u, 0u};
+    for (int k = 0; k < U; ++k) s[k] = load_object(in, u0 + k, n, col);
     if (mode != 1) {
 #pragma unroll
       for (int k = 0; k < U; ++k) {
@@ -110,32 +107,30 @@ __global__ __launch_bounds__(kBlock) void k_halve(const uint64_t *in, uint64_t *
       }
     }
 #pragma unroll
-    for (int k = 0; k < U; ++k)
-      if (u0 + k < n) st<true>(out + (u0 + k) * kWave + lane, s[k]);
+    for (int k = 0; k < U; ++k) store_object(out, u0 + k, n, lane, s[k]);
   }
 }
 
 // out[u] = in[u].Skew() (column x rotated left by x) or InvSkew() (right)
 template <int U>
 __global__ __launch_bounds__(kBlock) void k_skew(const uint64_t *in, uint64_t *out, uint32_t inverse, uint64_t n) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  // (the lane spelled out: through wave_lane() this kernel's listing changes)
+  const int lane = threadIdx.x & (kWave - 1), wib = wave_in_block();
   const uint32_t r = (inverse ? (uint32_t)lane : 64u - (uint32_t)lane) & 63u;  // the right-rotate
   const bool swap = (r & 32u) != 0;
-  const uint64_t groups = (n + U - 1) / U, stride = (uint64_t)gridDim.x * kWavesPerBlock;
-  for (uint64_t g = (uint64_t)blockIdx.x * kWavesPerBlock + wib; g < groups; g += stride) {
+  const WaveGroups at = wave_groups<U>(wib, n);
+  for (uint64_t g = at.first; g < at.groups; g += at.stride) {
     const uint64_t u0 = g * U;
     W s[U];
 #pragma unroll
-    for (int k = 0; k < U; ++k) s[k] = u0 + k < n ? ld<true>(in + (u0 + k) * kWave + lane) : W{0u, 0u};
+    for (int k = 0; k < U; ++k) s[k] = load_object(in, u0 + k, n, lane);
 #pragma unroll
     for (int k = 0; k < U; ++k) {
       const W x = swap ? W{s[k].hi, s[k].lo} : s[k];
       s[k] = W{__builtin_amdgcn_alignbit(x.hi, x.lo, r & 31u), __builtin_amdgcn_alignbit(x.lo, x.hi, r & 31u)};
     }
 #pragma unroll
-    for (int k = 0; k < U; ++k)
-      if (u0 + k < n) st<true>(out + (u0 + k) * kWave + lane, s[k]);
+    for (int k = 0; k < U; ++k) store_object(out, u0 + k, n, lane, s[k]);
   }
 }
 

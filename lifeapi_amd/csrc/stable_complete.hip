@@ -11,7 +11,6 @@ using namespace lifeapi_impl;
 
 namespace {
 
-constexpr size_t kState = 512, kStable = 10 * 512;
 // A full grid: this many blocks per CU (what the kernel's 156 VGPRs leave resident),
 // each wave with a stack of its own.  The
 // waves claim their objects, so a smaller grid (a smaller workspace) only
@@ -40,7 +39,7 @@ struct Args {
 int check_args(const char *fn, const Args &a) {
   const std::string f(fn);
   auto bad = [&](const char *what) { return fail(LIFEAPI_E_INVALID, (f + ": " + what + "%s").c_str()); };
-  if (a.n > SIZE_MAX / kStable) return bad("n too large");
+  if (a.n > SIZE_MAX / kStableBytes) return bad("n too large");
   if (a.flags & ~(kCompleteFlagMinimise | kCompleteFlagUseSeed)) return bad("unknown flag bits");
   if (a.max_depth == 0 || a.max_depth > kMaxDepth) return bad("max_depth outside 1..4096");
   if (a.node_budget > kMaxBudget) return bad("node_budget above 1 << 24");
@@ -52,8 +51,8 @@ int check_args(const char *fn, const Args &a) {
     const void *p;
     size_t bytes;
   };
-  const Range in[2] = {{a.planes, a.n * kStable}, {a.seeds, seeded ? (a.per_object_seeds ? a.n * kState : kState) : 0}};
-  const Range out[3] = {{a.best, a.n * kState}, {a.result, a.n}, {a.nodes, a.nodes ? a.n * 8 : 0}};
+  const Range in[2] = {{a.planes, a.n * kStableBytes}, {a.seeds, seeded ? (a.per_object_seeds ? a.n * kStateBytes : kStateBytes) : 0}};
+  const Range out[3] = {{a.best, a.n * kStateBytes}, {a.result, a.n}, {a.nodes, a.nodes ? a.n * 8 : 0}};
   for (const Range &o : out)
     for (const Range &i : in)
       if (o.bytes && i.bytes && ranges_overlap(o.p, o.bytes, i.p, i.bytes)) return bad("an output overlaps an input");
@@ -115,9 +114,9 @@ int lifeapi_stable_complete_batch_dev(const uint64_t *d_planes, const uint64_t *
   if (workspace_bytes < kCompleteHeaderBytes + stack_bytes(max_depth))
     return fail(LIFEAPI_E_INVALID, "%s: workspace below one wave's stack", fn);
   const bool seeded = (flags & kCompleteFlagUseSeed) != 0u;
-  const std::pair<const void *, size_t> arrays[5] = {{d_planes, n * kStable},
-                                                    {d_seeds, seeded ? (per_object_seeds ? n * kState : kState) : 0},
-                                                    {d_best, n * kState},
+  const std::pair<const void *, size_t> arrays[5] = {{d_planes, n * kStableBytes},
+                                                    {d_seeds, seeded ? (per_object_seeds ? n * kStateBytes : kStateBytes) : 0},
+                                                    {d_best, n * kStateBytes},
                                                     {d_result, n},
                                                     {d_nodes, d_nodes ? n * 8 : 0}};
   for (const auto &r : arrays)
@@ -133,7 +132,7 @@ int lifeapi_stable_complete_batch_dev(const uint64_t *d_planes, const uint64_t *
   if (e != hipSuccess) return fail_hip(e, "lifeapi_stable_complete_batch_dev: clearing the claim counter");
   Grid g{waves};
   g.cus = cus;
-  return launch(k_stable_complete, "k_stable_complete launch", g, stream, Written{d_best, (uint64_t)n * kState},
+  return launch(k_stable_complete, "k_stable_complete launch", g, stream, Written{d_best, (uint64_t)n * kStateBytes},
                 d_planes, seeded ? d_seeds : nullptr, per_object_seeds ? 1u : 0u, flags,
                 (uint32_t)(node_budget ? node_budget : kDefaultBudget), max_depth, d_best, d_result, d_nodes,
                 (unsigned long long *)d_workspace, (char *)d_workspace + kCompleteHeaderBytes, waves, (uint64_t)n);
@@ -161,8 +160,8 @@ int lifeapi_stable_complete_batch(const uint64_t *planes, const uint64_t *seeds,
                                              max_depth, (uint64_t *)d[1], (uint8_t *)d[2],
                                              counted ? (uint64_t *)d[4] : nullptr, m, ws, bytes, s);
   };
-  const HostIO in{planes, nullptr, kStable}, b{nullptr, best, kState}, r{nullptr, result, 1},
-      sd{seeded ? seeds : kNoSeed, nullptr, kState, !(seeded && per)};
+  const HostIO in{planes, nullptr, kStableBytes}, b{nullptr, best, kStateBytes}, r{nullptr, result, 1},
+      sd{seeded ? seeds : kNoSeed, nullptr, kStateBytes, !(seeded && per)};
   if (counted) return host_batch(n, device, {in, b, r, sd, {nullptr, nodes, 8}}, fn);
   return host_batch(n, device, {in, b, r, sd}, fn);
 }

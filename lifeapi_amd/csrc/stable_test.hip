@@ -9,7 +9,6 @@ using namespace lifeapi_impl;
 
 namespace {
 
-constexpr size_t kState = 512, kStable = 10 * 512;
 // The strip passes' waves loop over the batch from a grid of at most this many
 // blocks per CU (their work is bound by the 5 KiB they load).  The lookahead
 // kernels take one wave per LifeStable instead (Grid{n}; their loop only serves
@@ -20,30 +19,6 @@ constexpr size_t kState = 512, kStable = 10 * 512;
 // (1M objects, PropagateAndTest: 228 ms with 3 blocks per CU, 171 ms with 8).
 constexpr int kBlocksPerCu = 8;
 
-struct Arg {
-  const char *name;
-  const void *p;
-  size_t bytes;  // in all
-  bool align8;
-};
-
-int check_ptr(const char *fn, const Arg &a) {
-  if (!a.p) return fail(LIFEAPI_E_INVALID, (std::string(fn) + ": null " + a.name + "%s").c_str());
-  if (a.align8 && !aligned8(a.p))
-    return fail(LIFEAPI_E_INVALID, (std::string(fn) + ": misaligned " + a.name + "%s").c_str());
-  return LIFEAPI_OK;
-}
-// the planes clear of every other array of the call
-int check_clear(const char *fn, const Arg &planes, std::initializer_list<Arg> others) {
-  for (const Arg &o : others)
-    if (ranges_overlap(planes.p, planes.bytes, o.p, o.bytes))
-      return fail(LIFEAPI_E_INVALID, (std::string(fn) + ": " + o.name + " overlaps " + planes.name + "%s").c_str());
-  return LIFEAPI_OK;
-}
-int check_n(const char *fn, size_t n) {
-  return n > SIZE_MAX / kStable ? fail(LIFEAPI_E_INVALID, "%s: n too large", fn) : LIFEAPI_OK;
-}
-
 using StripFn = void (*)(uint64_t *, const uint8_t *, uint8_t *, uint64_t, uint32_t);
 const StripFn kStripPasses[6] = {k_stable_strip<0>, k_stable_strip<1>, k_stable_strip<2>,
                                  k_stable_strip<3>, k_stable_strip<4>, k_stable_strip<5>};
@@ -52,17 +27,17 @@ int test_launch(const char *fn, bool test_unknowns, uint64_t *d_planes, const ui
                 uint8_t *d_flags, size_t n, uint32_t max_iters, void *stream) {
   if (n == 0) return LIFEAPI_OK;
   int rc = check_n(fn, n);
-  const Arg pl{"d_planes", d_planes, n * kStable, true}, fl{"d_flags", d_flags, n, false},
-      ce{"d_cells", d_cells, per_object_cells ? n * kState : kState, true};
+  const Arg pl{"d_planes", d_planes, n * kStableBytes, true}, fl{"d_flags", d_flags, n, false},
+      ce{"d_cells", d_cells, per_object_cells ? n * kStateBytes : kStateBytes, true};
   if (rc == LIFEAPI_OK) rc = check_ptr(fn, pl);
   if (rc == LIFEAPI_OK) rc = check_ptr(fn, fl);
   if (rc == LIFEAPI_OK && test_unknowns) rc = check_ptr(fn, ce);
-  if (rc == LIFEAPI_OK) rc = check_clear(fn, pl, {fl});
-  if (rc == LIFEAPI_OK && test_unknowns) rc = check_clear(fn, pl, {ce});
+  if (rc == LIFEAPI_OK) rc = check_clear(fn, fl, {pl});
+  if (rc == LIFEAPI_OK && test_unknowns) rc = check_clear(fn, ce, {pl});
   if (rc != LIFEAPI_OK) return rc;
   return launch(test_unknowns ? k_stable_test<0> : k_stable_test<1>,
                 test_unknowns ? "k_stable_test<0> launch" : "k_stable_test<1> launch", Grid{n}, stream,
-                Written{d_planes, (uint64_t)n * kStable}, d_planes, d_cells, per_object_cells ? 1u : 0u, d_flags, n,
+                Written{d_planes, (uint64_t)n * kStableBytes}, d_planes, d_cells, per_object_cells ? 1u : 0u, d_flags, n,
                 max_iters ? max_iters : 1u << 20);
 }
 
@@ -76,14 +51,15 @@ int lifeapi_stable_strip_pass_batch_dev(uint64_t *d_planes, const uint8_t *d_col
   if (pass < 0 || pass > 5) return fail(LIFEAPI_E_INVALID, "%s: pass outside 0..5", fn);
   if (n == 0) return LIFEAPI_OK;
   int rc = check_n(fn, n);
-  const Arg pl{"d_planes", d_planes, n * kStable, true}, co{"d_columns", d_columns, n, false},
+  const Arg pl{"d_planes", d_planes, n * kStableBytes, true}, co{"d_columns", d_columns, n, false},
       fl{"d_flags", d_flags, n, false};
   for (const Arg *a : {&pl, &co, &fl})
     if (rc == LIFEAPI_OK) rc = check_ptr(fn, *a);
-  if (rc == LIFEAPI_OK) rc = check_clear(fn, pl, {co, fl});
+  for (const Arg *a : {&co, &fl})
+    if (rc == LIFEAPI_OK) rc = check_clear(fn, *a, {pl});
   if (rc != LIFEAPI_OK) return rc;
   return launch(kStripPasses[pass], "k_stable_strip launch", Grid{n, kBlocksPerCu}, stream,
-                Written{d_planes, (uint64_t)n * kStable}, d_planes, d_columns, d_flags, n,
+                Written{d_planes, (uint64_t)n * kStableBytes}, d_planes, d_columns, d_flags, n,
                 max_iters ? max_iters : 1u << 20);
 }
 

@@ -14,22 +14,6 @@ namespace {
 // universes per wave (their loads issued first)
 constexpr int kTransformU = 4, kSymmetricizeU = 4, kBoundsU = 4, kOrbitU = 2;
 
-// one wave per group of U universes, a wave for every group (the kernels'
-// loops only run again on a grid capped at 2^30 blocks)
-template <class... P, class... A>
-int launch_groups(void (*kernel)(P...), const char *what, int U, void *stream, uint64_t *d_out, size_t n, A... args) {
-  return launch(kernel, what, Grid{(n + U - 1) / U}, stream,
-                d_out ? Written{d_out, (uint64_t)n * 512} : kWritesNoBatch, args...);
-}
-
-// a per-universe output of `bytes` each: aligned, clear of the states
-int check_side(const void *p, size_t align, size_t bytes, const void *d_states, size_t n, const char *what) {
-  if ((uintptr_t)p & (align - 1)) return fail(LIFEAPI_E_INVALID, "misaligned output of %s", what);
-  if (n > SIZE_MAX / bytes || ranges_overlap(p, n * bytes, d_states, n * 512))
-    return fail(LIFEAPI_E_INVALID, "an output of %s overlaps the input batch", what);
-  return LIFEAPI_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -41,9 +25,9 @@ int lifeapi_transform_batch_dev(const uint64_t *d_in, uint64_t *d_out, size_t n,
   const int rc = check_batch(d_in, d_out, n);
   if (rc != LIFEAPI_OK) return rc;
   const Affine a = backwards(moved(kTransforms[transform], dx, dy));
-  return a.transpose ? launch_groups(k_transform<true, kTransformU>, "k_transform launch", kTransformU, stream, d_out,
+  return a.transpose ? launch_groups(k_transform<true, kTransformU>, "k_transform launch", kTransformU, stream, d_out, kStateBytes,
                                      n, d_in, d_out, a, n)
-                     : launch_groups(k_transform<false, kTransformU>, "k_transform launch", kTransformU, stream, d_out,
+                     : launch_groups(k_transform<false, kTransformU>, "k_transform launch", kTransformU, stream, d_out, kStateBytes,
                                      n, d_in, d_out, a, n);
 }
 
@@ -57,7 +41,7 @@ int lifeapi_symmetricize_batch_dev(const uint64_t *d_in, uint64_t *d_out, size_t
   const int rc = check_batch(d_in, d_out, n);
   if (rc != LIFEAPI_OK) return rc;
   const Affine2 maps{{backwards(m[0]), backwards(m[1])}};
-  return launch_groups(k_symmetricize<kSymmetricizeU>, "k_symmetricize launch", kSymmetricizeU, stream, d_out, n, d_in,
+  return launch_groups(k_symmetricize<kSymmetricizeU>, "k_symmetricize launch", kSymmetricizeU, stream, d_out, kStateBytes, n, d_in,
                        d_out, maps, (uint32_t)rounds, n);
 }
 
@@ -78,9 +62,9 @@ int lifeapi_transform_offsets_batch_dev(const uint64_t *d_in, uint64_t *d_out, s
   if (rc != LIFEAPI_OK) return rc;
   const Forward base = kTransforms[transform];
   return base.swap ? launch_groups(k_transform_offsets<true, kTransformU>, "k_transform_offsets launch", kTransformU,
-                                   stream, d_out, n, d_in, d_out, base, d_offsets, n)
+                                   stream, d_out, kStateBytes, n, d_in, d_out, base, d_offsets, n)
                    : launch_groups(k_transform_offsets<false, kTransformU>, "k_transform_offsets launch", kTransformU,
-                                   stream, d_out, n, d_in, d_out, base, d_offsets, n);
+                                   stream, d_out, kStateBytes, n, d_in, d_out, base, d_offsets, n);
 }
 
 int lifeapi_symmetricize_offsets_batch_dev(const uint64_t *d_in, uint64_t *d_out, size_t n, uint32_t symmetry,
@@ -94,7 +78,7 @@ int lifeapi_symmetricize_offsets_batch_dev(const uint64_t *d_in, uint64_t *d_out
   if (rc == LIFEAPI_OK) rc = check_offsets(d_offsets, d_out, n, "lifeapi_symmetricize_offsets_batch_dev");
   if (rc != LIFEAPI_OK) return rc;
   return launch_groups(k_symmetricize_offsets<kSymmetricizeU>, "k_symmetricize_offsets launch", kSymmetricizeU, stream,
-                       d_out, n, d_in, d_out, symmetry, d_offsets, n);
+                       d_out, kStateBytes, n, d_in, d_out, symmetry, d_offsets, n);
 }
 
 int lifeapi_bounds_batch_dev(const uint64_t *d_states, int32_t *d_bounds, size_t n, void *stream) {
@@ -103,7 +87,7 @@ int lifeapi_bounds_batch_dev(const uint64_t *d_states, int32_t *d_bounds, size_t
   int rc = check_batch(d_states, d_states, n);
   if (rc == LIFEAPI_OK) rc = check_side(d_bounds, 4, 16, d_states, n, "lifeapi_bounds_batch_dev");
   if (rc != LIFEAPI_OK) return rc;
-  return launch_groups(k_bounds<kBoundsU>, "k_bounds launch", kBoundsU, stream, nullptr, n, d_states, d_bounds, n);
+  return launch_groups(k_bounds<kBoundsU>, "k_bounds launch", kBoundsU, stream, nullptr, 0, n, d_states, d_bounds, n);
 }
 
 int lifeapi_symmetry_orbit_batch_dev(const uint64_t *d_states, uint64_t *d_images, uint8_t *d_first, size_t n,
@@ -118,8 +102,8 @@ int lifeapi_symmetry_orbit_batch_dev(const uint64_t *d_states, uint64_t *d_image
   if (rc == LIFEAPI_OK && d_images && d_first && ranges_overlap(d_first, n, d_images, n * 8 * 512))
     rc = fail(LIFEAPI_E_INVALID, "lifeapi_symmetry_orbit_batch_dev: d_first overlaps d_images%s");
   if (rc != LIFEAPI_OK) return rc;
-  return launch(k_symmetry_orbit<kOrbitU>, "k_symmetry_orbit launch", Grid{(n + kOrbitU - 1) / kOrbitU}, stream,
-                d_images ? Written{d_images, (uint64_t)n * 8 * 512} : kWritesNoBatch, d_states, d_images, d_first, n);
+  return launch_groups(k_symmetry_orbit<kOrbitU>, "k_symmetry_orbit launch", kOrbitU, stream, d_images, 8 * kStateBytes,
+                       n, d_states, d_images, d_first, n);
 }
 
 }  // extern "C"

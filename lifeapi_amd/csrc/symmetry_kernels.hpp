@@ -278,15 +278,15 @@ __device__ __forceinline__ void affine_apply(W (&t)[U], const W (&s)[U], const A
 // whole before it stores them and touches no other's.
 template <bool TRANSPOSE, int U>
 __global__ __launch_bounds__(kBlock) void k_transform(const uint64_t *in, uint64_t *out, Affine a, uint64_t n) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  const int lane = wave_lane(), wib = wave_in_block();
   const int col = affine_col(lane, a);
   TransposeLane c;
   if constexpr (TRANSPOSE) c = transpose_lane(lane);
-  const uint64_t groups = (n + U - 1) / U, stride = (uint64_t)gridDim.x * kWavesPerBlock;
-  for (uint64_t g = (uint64_t)blockIdx.x * kWavesPerBlock + wib; g < groups; g += stride) {
+  const WaveGroups at = wave_groups<U>(wib, n);
+  for (uint64_t g = at.first; g < at.groups; g += at.stride) {
     const uint64_t u0 = g * U;
     W s[U];
+    // (spelled out: through load_object the listing of k_transform<false> changes)
 #pragma unroll
     for (int k = 0; k < U; ++k) s[k] = u0 + k < n ? ld<true>(in + (u0 + k) * kWave + col) : W{0u, 0u};
     affine_rows<U>(s, a);
@@ -295,8 +295,7 @@ __global__ __launch_bounds__(kBlock) void k_transform(const uint64_t *in, uint64
       for (int k = 0; k < U; ++k) s[k] = transpose64(s[k], c);
     }
 #pragma unroll
-    for (int k = 0; k < U; ++k)
-      if (u0 + k < n) st<true>(out + (u0 + k) * kWave + lane, s[k]);
+    for (int k = 0; k < U; ++k) store_object(out, u0 + k, n, lane, s[k]);
   }
 }
 
@@ -308,15 +307,14 @@ struct Affine2 {
 template <int U>
 __global__ __launch_bounds__(kBlock) void k_symmetricize(const uint64_t *in, uint64_t *out, Affine2 maps,
                                                          uint32_t rounds, uint64_t n) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  const int lane = wave_lane(), wib = wave_in_block();
   const TransposeLane c = transpose_lane(lane);
-  const uint64_t groups = (n + U - 1) / U, stride = (uint64_t)gridDim.x * kWavesPerBlock;
-  for (uint64_t g = (uint64_t)blockIdx.x * kWavesPerBlock + wib; g < groups; g += stride) {
+  const WaveGroups at = wave_groups<U>(wib, n);
+  for (uint64_t g = at.first; g < at.groups; g += at.stride) {
     const uint64_t u0 = g * U;
     W acc[U];
 #pragma unroll
-    for (int k = 0; k < U; ++k) acc[k] = u0 + k < n ? ld<true>(in + (u0 + k) * kWave + lane) : W{0u, 0u};
+    for (int k = 0; k < U; ++k) acc[k] = load_object(in, u0 + k, n, lane);
 #pragma unroll
     for (int r = 0; r < 2; ++r)
       if ((uint32_t)r < rounds) {
@@ -326,8 +324,7 @@ __global__ __launch_bounds__(kBlock) void k_symmetricize(const uint64_t *in, uin
         for (int k = 0; k < U; ++k) acc[k] = W{acc[k].lo | t[k].lo, acc[k].hi | t[k].hi};
       }
 #pragma unroll
-    for (int k = 0; k < U; ++k)
-      if (u0 + k < n) st<true>(out + (u0 + k) * kWave + lane, acc[k]);
+    for (int k = 0; k < U; ++k) store_object(out, u0 + k, n, lane, acc[k]);
   }
 }
 
@@ -347,12 +344,11 @@ __device__ __forceinline__ int offset_word(int o, int i) { return __builtin_amdg
 template <bool TRANSPOSE, int U>
 __global__ __launch_bounds__(kBlock) void k_transform_offsets(const uint64_t *in, uint64_t *out, Forward base,
                                                               const int32_t *__restrict__ offsets, uint64_t n) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  const int lane = wave_lane(), wib = wave_in_block();
   TransposeLane c;
   if constexpr (TRANSPOSE) c = transpose_lane(lane);
-  const uint64_t groups = (n + U - 1) / U, stride = (uint64_t)gridDim.x * kWavesPerBlock;
-  for (uint64_t g = (uint64_t)blockIdx.x * kWavesPerBlock + wib; g < groups; g += stride) {
+  const WaveGroups at = wave_groups<U>(wib, n);
+  for (uint64_t g = at.first; g < at.groups; g += at.stride) {
     const uint64_t u0 = g * U;
     const int o = load_offsets<U>(offsets, u0, n, lane);
     Affine a[U];
@@ -360,7 +356,7 @@ __global__ __launch_bounds__(kBlock) void k_transform_offsets(const uint64_t *in
 #pragma unroll
     for (int k = 0; k < U; ++k) {
       a[k] = backwards(moved(base, offset_word(o, 2 * k), offset_word(o, 2 * k + 1)));
-      s[k] = u0 + k < n ? ld<true>(in + (u0 + k) * kWave + affine_col(lane, a[k])) : W{0u, 0u};
+      s[k] = load_object(in, u0 + k, n, affine_col(lane, a[k]));
     }
 #pragma unroll
     for (int k = 0; k < U; ++k) {
@@ -370,8 +366,7 @@ __global__ __launch_bounds__(kBlock) void k_transform_offsets(const uint64_t *in
       if constexpr (TRANSPOSE) s[k] = transpose64(s[k], c);
     }
 #pragma unroll
-    for (int k = 0; k < U; ++k)
-      if (u0 + k < n) st<true>(out + (u0 + k) * kWave + lane, s[k]);
+    for (int k = 0; k < U; ++k) store_object(out, u0 + k, n, lane, s[k]);
   }
 }
 
@@ -382,16 +377,15 @@ template <int U>
 __global__ __launch_bounds__(kBlock) void k_symmetricize_offsets(const uint64_t *in, uint64_t *out,
                                                                  uint32_t symmetry,
                                                                  const int32_t *__restrict__ offsets, uint64_t n) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  const int lane = wave_lane(), wib = wave_in_block();
   const TransposeLane c = transpose_lane(lane);
-  const uint64_t groups = (n + U - 1) / U, stride = (uint64_t)gridDim.x * kWavesPerBlock;
-  for (uint64_t g = (uint64_t)blockIdx.x * kWavesPerBlock + wib; g < groups; g += stride) {
+  const WaveGroups at = wave_groups<U>(wib, n);
+  for (uint64_t g = at.first; g < at.groups; g += at.stride) {
     const uint64_t u0 = g * U;
     const int o = load_offsets<U>(offsets, u0, n, lane);
     W acc[U];
 #pragma unroll
-    for (int k = 0; k < U; ++k) acc[k] = u0 + k < n ? ld<true>(in + (u0 + k) * kWave + lane) : W{0u, 0u};
+    for (int k = 0; k < U; ++k) acc[k] = load_object(in, u0 + k, n, lane);
     // one universe after another, its maps built just before they are applied
     // (building all U universes' maps first and applying each round stage by
     // stage across them was measured slower: 100 SGPRs, 7 waves per SIMD,
@@ -409,8 +403,7 @@ __global__ __launch_bounds__(kBlock) void k_symmetricize_offsets(const uint64_t 
         }
     }
 #pragma unroll
-    for (int k = 0; k < U; ++k)
-      if (u0 + k < n) st<true>(out + (u0 + k) * kWave + lane, acc[k]);
+    for (int k = 0; k < U; ++k) store_object(out, u0 + k, n, lane, acc[k]);
   }
 }
 
@@ -434,21 +427,20 @@ __device__ __forceinline__ uint64_t wave_or_u64_dpp(W v) {
 template <int U>
 __global__ __launch_bounds__(kBlock) void k_bounds(const uint64_t *__restrict__ in, int32_t *__restrict__ bounds,
                                                    uint64_t n) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
-  const uint64_t groups = (n + U - 1) / U, stride = (uint64_t)gridDim.x * kWavesPerBlock;
-  for (uint64_t g = (uint64_t)blockIdx.x * kWavesPerBlock + wib; g < groups; g += stride) {
+  const int lane = wave_lane(), wib = wave_in_block();
+  const WaveGroups at = wave_groups<U>(wib, n);
+  for (uint64_t g = at.first; g < at.groups; g += at.stride) {
     const uint64_t u0 = g * U;
     W s[U];
 #pragma unroll
-    for (int k = 0; k < U; ++k) s[k] = u0 + k < n ? ld<true>(in + (u0 + k) * kWave + lane) : W{0u, 0u};
+    for (int k = 0; k < U; ++k) s[k] = load_object(in, u0 + k, n, lane);
     int h = 0;
 #pragma unroll
     for (int k = 0; k < U; ++k) {
       const Bounds b = bounds_of(__ballot((s[k].lo | s[k].hi) != 0u), wave_or_u64_dpp(s[k]));
       h = lane == 4 * k ? b.left : lane == 4 * k + 1 ? b.top : lane == 4 * k + 2 ? b.right : lane == 4 * k + 3 ? b.bottom : h;
     }
-    if (lane < 4 * U && u0 + (uint64_t)(lane >> 2) < n) bounds[u0 * 4 + lane] = h;
+    if (holds_scalar<U, 4>(u0, n, lane)) bounds[u0 * 4 + lane] = h;
   }
 }
 
@@ -480,15 +472,14 @@ __global__ __launch_bounds__(kBlock) void k_symmetry_orbit(const uint64_t *__res
   constexpr bool kT[8] = {false, false, true, false, true, true, true, false};
   constexpr bool kNegCol[8] = {false, false, false, true, true, true, false, true};
   constexpr bool kNegRow[8] = {false, true, false, false, true, false, true, true};
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  const int lane = wave_lane(), wib = wave_in_block();
   const TransposeLane c = transpose_lane(lane);
-  const uint64_t groups = (n + U - 1) / U, stride = (uint64_t)gridDim.x * kWavesPerBlock;
-  for (uint64_t g = (uint64_t)blockIdx.x * kWavesPerBlock + wib; g < groups; g += stride) {
+  const WaveGroups at = wave_groups<U>(wib, n);
+  for (uint64_t g = at.first; g < at.groups; g += at.stride) {
     const uint64_t u0 = g * U;
     W s[U];
 #pragma unroll
-    for (int k = 0; k < U; ++k) s[k] = u0 + k < n ? ld<true>(in + (u0 + k) * kWave + lane) : W{0u, 0u};
+    for (int k = 0; k < U; ++k) s[k] = load_object(in, u0 + k, n, lane);
     uint32_t h = 0;
 #pragma unroll
     for (int k = 0; k < U; ++k) {
@@ -515,6 +506,8 @@ __global__ __launch_bounds__(kBlock) void k_symmetry_orbit(const uint64_t *__res
         for (int j = 0; j < i; ++j)
           seen = seen || __ballot(((img[i].lo ^ img[j].lo) | (img[i].hi ^ img[j].hi)) != 0u) == 0ull;
         mask |= seen ? 0u : 1u << i;
+        // (this guard and the one on `first` spelled out: through store_object
+        // and holds_scalar this kernel's listing changes)
         if (images && u0 + k < n) st<true>(images + ((u0 + k) * 8 + i) * kWave + lane, img[i]);
       }
       h = lane == k ? mask : h;

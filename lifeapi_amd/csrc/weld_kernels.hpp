@@ -7,8 +7,8 @@
 // frozen2, frozen1, frozen0} x 64 words, LifeStable = {state, unknown, live2,
 // live3, dead0, dead1, dead2, dead4, dead5, dead6} x 64 words (member order).
 // ZOI() is the 3 x 3 dilation (rot_up / rot_dn, then the neighbour columns by
-// DPP); the inclusive 3 x 3 count is the network of interaction_planes
-// (match_kernels.hpp).  All four functions are total: nothing is assumed about
+// DPP); the inclusive 3 x 3 count is count4 (match_kernels.hpp); the loop over
+// the groups is wave_groups.hpp's.  All four functions are total: nothing is assumed about
 // the planes (frozen counts on live cells, `required` unrelated to the state,
 // `active` over the state are all computed as the reference computes them).
 //
@@ -62,24 +62,6 @@ __device__ __forceinline__ uint64_t zoi(uint64_t a, int lane) {
   return join(lut3<kOr3>(v, L, R));
 }
 
-// the inclusive 3 x 3 count as four planes (NeighbourCount.hpp:40-70)
-struct Count4 {
-  uint64_t b3, b2, b1, b0;
-  __device__ __forceinline__ uint64_t exactly(unsigned n) const {
-    return (n & 1 ? b0 : ~b0) & (n & 2 ? b1 : ~b1) & (n & 4 ? b2 : ~b2) & (n & 8 ? b3 : ~b3);
-  }
-};
-__device__ __forceinline__ Count4 count4(uint64_t s, int lane) {
-  const W a = split(s), up = rot_up(a), dn = rot_dn(a);
-  const W c0 = lut3<kXor3>(up, dn, a), c1 = lut3<kMaj>(up, dn, a);
-  W L0, R0, L1, R1;
-  neighbours<XDPP>(c0, c1, L0, R0, L1, R1, nullptr, lane);
-  const uint64_t fs = join(lut3<kXor3>(L0, c0, R0)), fc = join(lut3<kMaj>(L0, c0, R0));
-  const uint64_t cs = join(lut3<kXor3>(L1, c1, R1)), cc = join(lut3<kMaj>(L1, c1, R1));
-  const uint64_t carry = fc & cs;
-  return Count4{cc & carry, cc ^ carry, fc ^ cs, fs};
-}
-
 // count + the frozen 3-bit number, bit3 = count.bit3 ^ the last carry
 // (LifeWeld.hpp:295-299); Step() uses bits 2..0 of it (:177-185)
 __device__ __forceinline__ Count4 add_frozen(const Count4 &c, uint64_t f2, uint64_t f1, uint64_t f0) {
@@ -93,7 +75,9 @@ __device__ __forceinline__ uint64_t rule(const Count4 &s, uint64_t state) {
   return (s.b0 ^ s.b2) & (s.b1 ^ s.b2) & (state | s.b0);
 }
 
-__device__ __forceinline__ uint64_t ldw(const uint64_t *p) { return __builtin_nontemporal_load(p); }
+// a plane held as one 64-bit word, stored as ld<true> loads (spelled out, not
+// st<true>(p, split(v)): the trip through the halves changes the listings of
+// k_weld_from_required and k_weld_to_target)
 __device__ __forceinline__ void stw(uint64_t *p, uint64_t v) { __builtin_nontemporal_store(v, p); }
 
 // welds[u] = LifeWeld::FromRequired(states[u], required[per ? u : 0])
@@ -101,17 +85,16 @@ template <int U>
 __global__ __launch_bounds__(kBlock) void k_weld_from_required(const uint64_t *__restrict__ states,
                                                                const uint64_t *__restrict__ required, uint32_t per,
                                                                uint64_t *__restrict__ welds, uint64_t n) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
-  const uint64_t groups = (n + U - 1) / U, stride = (uint64_t)gridDim.x * kWavesPerBlock;
-  for (uint64_t g = (uint64_t)blockIdx.x * kWavesPerBlock + wib; g < groups; g += stride) {
+  const int lane = wave_lane(), wib = wave_in_block();
+  const WaveGroups at = wave_groups<U>(wib, n);
+  for (uint64_t g = at.first; g < at.groups; g += at.stride) {
     const uint64_t u0 = g * U;
     uint64_t s[U], r[U];
 #pragma unroll
     for (int k = 0; k < U; ++k) {
-      const bool ok = u0 + k < n;
-      s[k] = ok ? ldw(states + (u0 + k) * kWave + lane) : 0;
-      r[k] = ok ? (per ? ldw(required + (u0 + k) * kWave + lane) : required[lane]) : 0;
+      const bool ok = u0 + k < n;  // (one guard for the planes: a load_object each changes the listing)
+      s[k] = ok ? join(ld<true>(states + (u0 + k) * kWave + lane)) : 0;
+      r[k] = ok ? (per ? join(ld<true>(required + (u0 + k) * kWave + lane)) : required[lane]) : 0;
     }
 #pragma unroll
     for (int k = 0; k < U; ++k) {
@@ -121,7 +104,7 @@ __global__ __launch_bounds__(kBlock) void k_weld_from_required(const uint64_t *_
       // births the kept part would have on its own
       const uint64_t frozen = (za & r[k]) | (rule(count4(kept, lane), kept) & ~kept);
       const Count4 c = count4(stator, lane);
-      if (u0 + k < n) {
+      if (u0 + k < n) {  // (one guard for the planes, as above)
         uint64_t *q = welds + (u0 + k) * 4 * kWave + lane;
         stw(q, kept);
         stw(q + kWave, c.b2 & frozen);
@@ -137,23 +120,22 @@ template <int U>
 __global__ __launch_bounds__(kBlock) void k_weld_to_target(const uint64_t *__restrict__ welds,
                                                            uint64_t *__restrict__ wanted,
                                                            uint64_t *__restrict__ unwanted, uint64_t n) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
-  const uint64_t groups = (n + U - 1) / U, stride = (uint64_t)gridDim.x * kWavesPerBlock;
-  for (uint64_t g = (uint64_t)blockIdx.x * kWavesPerBlock + wib; g < groups; g += stride) {
+  const int lane = wave_lane(), wib = wave_in_block();
+  const WaveGroups at = wave_groups<U>(wib, n);
+  for (uint64_t g = at.first; g < at.groups; g += at.stride) {
     const uint64_t u0 = g * U;
     uint64_t s[U], f[U];
 #pragma unroll
     for (int k = 0; k < U; ++k) {
       const uint64_t *p = welds + (u0 + k) * 4 * kWave + lane;
-      const bool ok = u0 + k < n;
-      s[k] = ok ? ldw(p) : 0;
-      f[k] = ok ? ldw(p + kWave) | ldw(p + 2 * kWave) | ldw(p + 3 * kWave) : 0;
+      const bool ok = u0 + k < n;  // (one guard for the planes: a load_object each changes the listing)
+      s[k] = ok ? join(ld<true>(p)) : 0;
+      f[k] = ok ? join(ld<true>(p + kWave)) | join(ld<true>(p + 2 * kWave)) | join(ld<true>(p + 3 * kWave)) : 0;
     }
 #pragma unroll
     for (int k = 0; k < U; ++k) {
       const uint64_t uw = zoi(s[k] & ~f[k], lane) & ~s[k];
-      if (u0 + k < n) {
+      if (u0 + k < n) {  // (one guard for the planes, as above)
         stw(wanted + (u0 + k) * kWave + lane, s[k]);
         stw(unwanted + (u0 + k) * kWave + lane, uw);
       }
@@ -168,15 +150,15 @@ __global__ __launch_bounds__(kBlock) void k_weld_to_stable(const uint64_t *__res
                                                            const uint64_t *__restrict__ active, uint32_t per,
                                                            const uint64_t *__restrict__ mask, uint32_t duration,
                                                            uint64_t *__restrict__ stables, uint64_t n) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  const int lane = wave_lane(), wib = wave_in_block();
   const uint64_t m = mask ? mask[lane] : ~0ull;
-  const uint64_t stride = (uint64_t)gridDim.x * kWavesPerBlock;
-  for (uint64_t u = (uint64_t)blockIdx.x * kWavesPerBlock + wib; u < n; u += stride) {
+  const WaveGroups at = wave_groups<1>(wib, n);
+  for (uint64_t u = at.first; u < at.groups; u += at.stride) {
     const uint64_t *p = welds + u * 4 * kWave + lane;
-    const uint64_t s = ldw(p), f2 = ldw(p + kWave), f1 = ldw(p + 2 * kWave), f0 = ldw(p + 3 * kWave);
+    const uint64_t s = join(ld<true>(p)), f2 = join(ld<true>(p + kWave)), f1 = join(ld<true>(p + 2 * kWave)),
+                   f0 = join(ld<true>(p + 3 * kWave));
     uint64_t cur = s;
-    if (active && duration) cur |= per ? ldw(active + u * kWave + lane) : active[lane];
+    if (active && duration) cur |= per ? join(ld<true>(active + u * kWave + lane)) : active[lane];
 
     // ---- ToStable() (LifeWeld.hpp:279-325) ----
     const Count4 sc = count4(s, lane);
@@ -253,8 +235,7 @@ template <int U>
 __global__ __launch_bounds__(kBlock) void k_weld_interaction_offsets(const uint64_t *__restrict__ welds,
                                                                      const uint64_t *__restrict__ other,
                                                                      uint64_t *__restrict__ out, uint64_t n) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  const int lane = wave_lane(), wib = wave_in_block();
   W bp[7], bkeep;  // Mirrored(other)'s planes, 1..6 under its own mask, but
   W bdead2;        // dead2 kept unmasked as well: the first birth term masks it by a's side
   {
@@ -267,16 +248,16 @@ __global__ __launch_bounds__(kBlock) void k_weld_interaction_offsets(const uint6
 #pragma unroll
     for (int i = 1; i < 7; ++i) bp[i] = W{bp[i].lo & bkeep.lo, bp[i].hi & bkeep.hi};
   }
-  const uint64_t groups = (n + U - 1) / U, stride = (uint64_t)gridDim.x * kWavesPerBlock;
-  for (uint64_t g = (uint64_t)blockIdx.x * kWavesPerBlock + wib; g < groups; g += stride) {
+  const WaveGroups at = wave_groups<U>(wib, n);
+  for (uint64_t g = at.first; g < at.groups; g += at.stride) {
     const uint64_t u0 = g * U;
     W s[U], keep[U], acc[U], ap[U][7];
 #pragma unroll
     for (int k = 0; k < U; ++k) {
       const uint64_t *p = welds + (u0 + k) * 4 * kWave + lane;
-      const bool ok = u0 + k < n;
+      const bool ok = u0 + k < n;  // (one guard for the planes: a load_object each changes the listing)
       s[k] = ok ? ld<true>(p) : W{0u, 0u};
-      keep[k] = ok ? split(ldw(p + kWave) | ldw(p + 2 * kWave) | ldw(p + 3 * kWave)) : W{0u, 0u};
+      keep[k] = ok ? split(join(ld<true>(p + kWave)) | join(ld<true>(p + 2 * kWave)) | join(ld<true>(p + 3 * kWave))) : W{0u, 0u};
     }
 #pragma unroll
     for (int k = 0; k < U; ++k) {
@@ -307,8 +288,7 @@ __global__ __launch_bounds__(kBlock) void k_weld_interaction_offsets(const uint6
       dilate<U>(acc, src, bp[kPartner[i]], lane);
     }
 #pragma unroll
-    for (int k = 0; k < U; ++k)
-      if (u0 + k < n) st<true>(out + (u0 + k) * kWave + lane, acc[k]);
+    for (int k = 0; k < U; ++k) store_object(out, u0 + k, n, lane, acc[k]);
   }
 }
 
